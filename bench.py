@@ -21,6 +21,12 @@ of a group of launches are summed by ONE ncclAllReduce over xGMI on a comm strea
 the compute streams work on the next group.
 
 Prints ONE JSON line on rank 0.
+
+A plain run does only what `value` needs: set-up, preheat, the W warmup steps, the timed K steps, the result line
+(`value`, `ms_per_step`, and what the workload was).  `--full` adds everything else in the same process, after the timed
+region: the pipelined == synchronous checks, the kernel-alone / sustained / cold / sequential / other-math / 10-bin /
+flash-pair figures (`roofline`), the per-rank figures at N > 1 (`multi_gpu`), the CPU baseline and the LM comparison
+with the oracle.  `--dump-outputs DIR` writes the timed region's results (DIR/*.npy, float64) right after it.
 """
 from __future__ import annotations
 
@@ -45,6 +51,26 @@ SIMD_ISSUE_PEAK = 1024 * 2.4e9 / 2.0  # wave-instructions/s: 1024 SIMDs, one ins
 #                                       ~4.4 cycles (profiles/r05_valu_wallclock.txt: HIP-event wall clock, every CU busy;
 #                                       the 2.0 of profiles/r01_valu_rates.txt timed the OLDEST wave only, which the
 #                                       arbiter serves first): what binds this kernel is roofline.valu_pipe
+DUMP_MAX_ROWS = 200000         # --dump-outputs: 200 000 rows x (32 + 1) doubles = 52.8 MB, under the 64 MB a dump may take
+DUMP_SEED = 20211003
+
+
+def dump_outputs(dirname, results, capi):
+    """What the timed region handed its caller: the K result blocks (per pose [chi2, b(6), H upper (21), n_active, ...],
+    NID_REDUCED_LEN doubles) as reduced.npy with their step indices in reduced_steps.npy -- every row, or a fixed seeded
+    sample of DUMP_MAX_ROWS rows that always holds the last step --, and the last step unpacked (last_H, last_b,
+    last_chi2, last_n_active).  float64 throughout."""
+    os.makedirs(dirname, exist_ok=True)
+    K = results.shape[0]
+    if K > DUMP_MAX_ROWS:
+        rng = np.random.default_rng(DUMP_SEED)
+        rows = np.append(np.sort(rng.choice(K - 1, DUMP_MAX_ROWS - 1, replace=False)), K - 1)
+    else:
+        rows = np.arange(K)
+    H, b, chi2, na = capi.unpack_reduced(results[K - 1])
+    arrays = {"reduced": results[rows], "reduced_steps": rows, "last_H": H, "last_b": b, "last_chi2": [chi2], "last_n_active": [na]}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def parse():
@@ -76,13 +102,20 @@ def parse():
                     help="time cost-only evaluations (what LM trial poses need) instead of cost+Jacobian; not the metric")
     ap.add_argument("--strict", action="store_true",
                     help="NID_MATH_STRICT (every rounding of the reference path) instead of the default FAST math; not the metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the checks and side measurements (roofline, sustained, cold, "
+                         "sequential, other math mode, 10 bins, flash pair, per-rank figures, CPU baseline, LM against the "
+                         "oracle); a plain run measures `value` alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed region computed to DIR/*.npy (float64; at most %d of the K result rows, "
+                         "a fixed seeded sample beyond that, the last step always included)" % DUMP_MAX_ROWS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the LM comparison")
     ap.add_argument("--no-flash", action="store_true",
-                    help="skip the flash-pair leg (profiling passes: its launches run the SAME kernel and would be averaged into "
+                    help="--full: skip the flash-pair leg (profiling passes: its launches run the SAME kernel and would be averaged into "
                          "the per-kernel figures of a rocprofv3 --stats table)")
-    ap.add_argument("--quick", action="store_true", help="skip the sustained / cold / sequential / STRICT side measurements")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--sustained-seconds", type=float, default=1.5)
+    ap.add_argument("--quick", action="store_true", help="--full: skip the sustained / cold / sequential / STRICT side measurements")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget")
+    ap.add_argument("--sustained-seconds", type=float, default=1.5, help="--full: length of the sustained legs")
     ap.add_argument("--backend", default="rccl", choices=["rccl", "nccl", "gloo"],
                     help="rccl (= nccl): ncclAllReduce from C++ is the product path; gloo: the exchange goes through "
                          "torch.distributed on the host (nid_multi_set_exchange_hook) so that the multi-rank code path "
@@ -528,24 +561,91 @@ def main():
             shots.append(el)
             assert np.array_equal(r2, results)
         elapsed = float(np.median(shots))
-        # for continuity with BENCH_r05 (whose region ended when run(K) returned, no synchronisation behind it): the same
-        # five times in that definition -- reported, not `value`
-        r05_shots = []
-        for _ in range(5):
-            run(W, collect=False)
-            barrier()
-            t_a = time.perf_counter()
-            run(K)
-            r05_shots.append(time.perf_counter() - t_a)
         short_info = {"form": "launches (plan_split: <= 16 poses per launch, two streams)", "timed_region": "barrier + synchronise | run(K) | synchronise",
                       "value_from": "median of 11 identical timed regions (W warmup steps in front of each)",
-                      "first_shot_us": first_shot * 1e6, "us_per_shot": [x * 1e6 for x in shots],
-                      "without_trailing_synchronisation_us_per_shot": [x * 1e6 for x in r05_shots],
-                      "it_per_s_without_trailing_synchronisation": K / float(np.median(r05_shots))}
-    # sanity: every result is finite, and the pipelined result of the last step equals a synchronous evaluation of
-    # the same pose (every rank holds the same sums after the exchange)
+                      "first_shot_us": first_shot * 1e6, "us_per_shot": [x * 1e6 for x in shots]}
+        if args.full:
+            # for continuity with BENCH_r05 (whose region ended when run(K) returned, no synchronisation behind it): the same
+            # five times in that definition -- reported, not `value`
+            r05_shots = []
+            for _ in range(5):
+                run(W, collect=False)
+                barrier()
+                t_a = time.perf_counter()
+                run(K)
+                r05_shots.append(time.perf_counter() - t_a)
+            short_info["without_trailing_synchronisation_us_per_shot"] = [x * 1e6 for x in r05_shots]
+            short_info["it_per_s_without_trailing_synchronisation"] = K / float(np.median(r05_shots))
+    # sanity: every result is finite (a host-side look at what the timed region returned: every run), and -- --full --
+    # the pipelined result of the last step equals a synchronous evaluation of the same pose (every rank holds the same
+    # sums after the exchange)
     ablation = bool(os.environ.get("NID_HIP_LIB"))  # kernel-ablation builds (exp/) produce meaningless numbers
     assert ablation or (results.shape == (K, capi.NID_REDUCED_LEN) and np.all(np.isfinite(results)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results, capi)
+
+    def headline():
+        """The result line's fields that a plain run has: the timed region and what it ran."""
+        out = {
+            "metric": "NID GN iterations/sec (640x480 dense pair)" if args.config == "A" else
+                      f"NID GN iterations/sec ({pair.cols}x{pair.rows} dense pair)",
+            "value": K / elapsed,
+            "unit": "iterations/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": W,
+            "preheat_seconds": args.preheat_seconds,   # setup before the warmup steps: clocks + instruction caches (see --help)
+            "ms_per_step": elapsed / K * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong",   # one frame pair's cells over the ranks: the total work is fixed at every N (N = 1 is the curve's base)
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "value_is": ("pipelined evaluation throughput over independent candidate poses" if K > 64 or multi else
+                         "K independent candidate poses as ONE short sequence, from the call to the last 6x6 system in host memory plus the "
+                         "device synchronisation behind it; MEDIAN of 11 such regions (short_sequence.us_per_shot; round 5 reported one "
+                         "rehearsed shot without the trailing synchronisation: not comparable)")
+                        + "; dependent-chain rates: roofline.sequential, pose_error_vs_ref.lm_outer_iterations_per_s"
+                        + ("; sustained throughput of the pipeline: roofline.sustained" if not multi else "")
+                        + ("" if args.full else " (all of them with --full)"),
+            "short_sequence": short_info,
+            "math": {"mode": "STRICT" if args.strict else "FAST",
+                     "exceptions": "none in tests/ (both modes hold the same bounds; FAST re-decides the reference's border / clamp "
+                                   "decisions, and every sample within 1/8 of an end knot, with the reference's arithmetic). Cells "
+                                   "that pass only on the measured reference-noise term are pairs whose reference Jacobian is "
+                                   "rounding noise (constant target image: sweep seeds 50185, 71823, 564566); see "
+                                   "profiles/r05_parity_sweeps.txt"},
+            "config": {
+                "workload": f"{pair.cols}x{pair.rows} synthetic RGB-D pair, {pair.cell}x{pair.cell} cells of "
+                            f"{pair.rows // pair.cell}x{pair.cols // pair.cell} px, {args.bins}-bin cubic B-spline "
+                            f"histograms, cost+Jacobian+Huber 6x6 reduction per step, "
+                            f"{int((cnt >= 300).sum())} active cells",
+                "cells": ncell, "bins": args.bins,
+                "parallelism": ((f"cells/{world} ({args.partition})" if world > 1 else (f"cells/{args.shards} shards on one GPU ({args.partition})" if multi else "cells/1")))
+                               + ("" if not multi else (f" + {'RCCL ncclAllReduce from C++' if ((world > 1 and rccl) or args.rccl_one_rank) else ('gloo exchange hook' if world > 1 else 'host sum')}"
+                                                        f" of [{G * Bm},32] f64 per {G} launches")),
+                "pipelining": (f"{B} candidate poses per kernel launch, up to {min(16, capi.NID_SLOTS // B)} launches in flight on 2 "
+                               f"streams, each launch's 6x6 systems copied to pinned host memory behind it (nid_run_sequence)") if not multi else
+                              (f"{Bm} poses per launch, launches alternate between 2 compute streams per shard, one exchange per "
+                               f"{G} launches + D2H to pinned memory on a comm stream, 2 groups in flight (nid_multi_run_sequence)"),
+            },
+        }
+        if multi:
+            out["rccl_ranks_seen"] = rccl_ranks_seen if rccl_ranks_seen is not None else 0   # 0: the exchange does not use RCCL
+        if world > 1 and not rccl:
+            out["exchange"] = "gloo all-reduce over the control group (--backend gloo: a test transport, not the product's RCCL exchange)"
+        return out
+
+    if not args.full:
+        if args.cost_only and rank == 0:
+            print("[bench] --cost-only: cost evaluations without the Jacobian phase; not the BASELINE metric", file=sys.stderr)
+        if rank == 0:
+            print(json.dumps(headline()), file=result_out, flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     last = poses[(K - 1) % len(poses)]
     H, b, chi2, na = (m if multi else ctx).normal_equations(last, delta, want_jac=want_jac)
     Hp, bp, chi2p, nap = capi.unpack_reduced(results[K - 1])
@@ -856,60 +956,14 @@ def main():
                 fctx.close()
             except Exception as e:   # noqa: BLE001 -- a side measurement must not take the line down
                 roof["flash_pair"] = {"error": str(e)[:200]}
-        out = {
-            "metric": "NID GN iterations/sec (640x480 dense pair)" if args.config == "A" else
-                      f"NID GN iterations/sec ({pair.cols}x{pair.rows} dense pair)",
-            "value": K / elapsed,
-            "unit": "iterations/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": W,
-            "preheat_seconds": args.preheat_seconds,   # setup before the warmup steps: clocks + instruction caches (see --help)
-            "ms_per_step": elapsed / K * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong",   # one frame pair's cells over the ranks: the total work is fixed at every N (N = 1 is the curve's base)
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "value_is": ("pipelined evaluation throughput over independent candidate poses" if K > 64 or multi else
-                         "K independent candidate poses as ONE short sequence, from the call to the last 6x6 system in host memory plus the "
-                         "device synchronisation behind it; MEDIAN of 11 such regions (short_sequence.us_per_shot; round 5 reported one "
-                         "rehearsed shot without the trailing synchronisation: not comparable)")
-                        + "; dependent-chain rates: roofline.sequential, pose_error_vs_ref.lm_outer_iterations_per_s"
-                        + ("; sustained throughput of the pipeline: roofline.sustained" if not multi else ""),
-            "short_sequence": short_info,
-            "math": {"mode": "STRICT" if args.strict else "FAST",
-                     "exceptions": "none in tests/ (both modes hold the same bounds; FAST re-decides the reference's border / clamp "
-                                   "decisions, and every sample within 1/8 of an end knot, with the reference's arithmetic). Cells "
-                                   "that pass only on the measured reference-noise term are pairs whose reference Jacobian is "
-                                   "rounding noise (constant target image: sweep seeds 50185, 71823, 564566); see "
-                                   "profiles/r05_parity_sweeps.txt"},
-            "config": {
-                "workload": f"{pair.cols}x{pair.rows} synthetic RGB-D pair, {pair.cell}x{pair.cell} cells of "
-                            f"{pair.rows // pair.cell}x{pair.cols // pair.cell} px, {args.bins}-bin cubic B-spline "
-                            f"histograms, cost+Jacobian+Huber 6x6 reduction per step, "
-                            f"{int((cnt >= 300).sum())} active cells",
-                "cells": ncell, "bins": args.bins,
-                "parallelism": ((f"cells/{world} ({args.partition})" if world > 1 else (f"cells/{args.shards} shards on one GPU ({args.partition})" if multi else "cells/1")))
-                               + ("" if not multi else (f" + {'RCCL ncclAllReduce from C++' if ((world > 1 and rccl) or args.rccl_one_rank) else ('gloo exchange hook' if world > 1 else 'host sum')}"
-                                                        f" of [{G * Bm},32] f64 per {G} launches")),
-                "pipelining": (f"{B} candidate poses per kernel launch, up to {min(16, capi.NID_SLOTS // B)} launches in flight on 2 "
-                               f"streams, each launch's 6x6 systems copied to pinned host memory behind it (nid_run_sequence)") if not multi else
-                              (f"{Bm} poses per launch, launches alternate between 2 compute streams per shard, one exchange per "
-                               f"{G} launches + D2H to pinned memory on a comm stream, 2 groups in flight (nid_multi_run_sequence)"),
-            },
-            "roofline": roof,
-        }
-        if multi:
-            out["rccl_ranks_seen"] = rccl_ranks_seen if rccl_ranks_seen is not None else 0   # 0: the exchange does not use RCCL
+        out = headline()
+        out["roofline"] = roof
         if world > 1:
             out["multi_gpu"] = {"per_rank_kernel_ms": per_rank_kernel_ms, "poses_per_launch": Bm, "launches_per_exchange": G,
                                 "exchange_ms_per_group": exchange_ms, "exchange_bytes_per_group": G * Bm * capi.NID_REDUCED_LEN * 8,
                                 "kernel_ms_per_group": max(per_rank_kernel_ms) * G,
                                 "note": "one group = launches_per_exchange launches of poses_per_launch poses on every rank's cells + "
                                         "ONE exchange; the exchange runs on a comm stream beside the next group's launches"}
-        if world > 1 and not rccl:
-            out["exchange"] = "gloo all-reduce over the control group (--backend gloo: a test transport, not the product's RCCL exchange)"
         out["check"] = {"chi2": chi2, "n_active": int(na), "H00": float(H[0, 0]), "b0": float(b[0])}
         if not args.no_cpu_baseline and not multi:   # CPU legs: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(pair, args.bins, args.cpu_seconds)

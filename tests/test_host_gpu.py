@@ -505,6 +505,48 @@ def test_driver_standard_property_mode(capi, synth, pair_S, tmp_path):
     assert abs(final - want) < 1e-4 * max(1.0, want)   # %g print + pose re-derived from groundtruth.txt
 
 
+def test_bench_plain_run_and_dumped_outputs(capi, synth, tmp_path):
+    """bench.py without --full: one result line with the headline fields and none of the side measurements;
+    --dump-outputs writes the timed region's result blocks (float64), the same bits from two processes, and the last
+    step equals a synchronous evaluation of the last pose.  K <= 64 (the short-sequence form) dumps its K blocks too."""
+    import json
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = {}
+    for name, steps, warmup in (("a", 300, 70), ("b", 300, 70), ("short", 20, 5)):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                            str(warmup), "--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(r.stdout.strip().splitlines()) == 1, r.stdout
+        lines[name] = d = json.loads(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "iterations/s" and d["dtype"] == "f64"
+        assert abs(d["value"] * d["ms_per_step"] - 1e3) <= 1e-9 * 1e3
+        assert not ({"roofline", "check", "cpu_baseline", "pose_error_vs_ref", "multi_gpu"} & set(d))
+    sh = lines["short"]["short_sequence"]
+    assert len(sh["us_per_shot"]) == 11 and "without_trailing_synchronisation_us_per_shot" not in sh
+    names = ("reduced", "reduced_steps", "last_H", "last_b", "last_chi2", "last_n_active")
+    for n in names:
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float64 and np.array_equal(_bits(a), _bits(b)), n
+    red = np.load(tmp_path / "a" / "reduced.npy")
+    assert red.shape == (300, capi.NID_REDUCED_LEN) and np.array_equal(np.load(tmp_path / "a" / "reduced_steps.npy"), np.arange(300))
+    assert np.load(tmp_path / "short" / "reduced.npy").shape == (20, capi.NID_REDUCED_LEN)
+    pair = synth.make_pair("A")
+    ctx = capi.from_pair(pair, 8)
+    ctx.set_math_mode(capi.MATH_FAST)   # bench.py's default
+    ctx.compute_href(pair.pose_init)
+    last = bench.pose_trajectory(synth, pair, 256)[299 % 256]
+    H, b, chi2, na = ctx.normal_equations(last, float(np.sqrt(0.95)))
+    ctx.close()
+    assert np.array_equal(np.load(tmp_path / "a" / "last_H.npy"), H) and np.array_equal(np.load(tmp_path / "a" / "last_b.npy"), b)
+    assert np.load(tmp_path / "a" / "last_chi2.npy")[0] == chi2 and np.load(tmp_path / "a" / "last_n_active.npy")[0] == na
+    Hp, bp, chi2p, nap = capi.unpack_reduced(red[-1])
+    assert np.array_equal(Hp, H) and chi2p == chi2 and nap == na
+
+
 def test_bench_multi_rank_code_path_on_one_gpu(tmp_path):
     """bench.py --gpus 2 / 4 through torch.distributed.run on ONE box: the ranks share GPU 0 (RCCL refuses two ranks
     per device), so the exchange goes through the library's exchange hook over gloo instead of ncclAllReduce --
@@ -516,18 +558,18 @@ def test_bench_multi_rank_code_path_on_one_gpu(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     bench = os.path.join(root, "bench.py")
-    one = subprocess.run([sys.executable, bench, "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--quick"],
+    one = subprocess.run([sys.executable, bench, "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--quick"],
                          capture_output=True, text=True, env=env, timeout=600)
     assert one.returncode == 0, one.stderr[-2000:]
     r1 = json.loads(one.stdout.strip().splitlines()[-1])
     assert r1["scaling"] == "strong" and r1["n_gpus"] == 1
-    sh = subprocess.run([sys.executable, bench, "--steps", "300", "--warmup", "70", "--no-cpu-baseline", "--shards", "3"],
+    sh = subprocess.run([sys.executable, bench, "--full", "--steps", "300", "--warmup", "70", "--no-cpu-baseline", "--shards", "3"],
                         capture_output=True, text=True, env=env, timeout=600)
     assert sh.returncode == 0, sh.stderr[-2000:]
     assert "3 shards" in json.loads(sh.stdout.strip().splitlines()[-1])["config"]["parallelism"]
     # the RCCL data path inside a process that has PyTorch (and its bundled ROCm libraries) loaded, as the driver's
     # multi-GPU runs have: communicator of one rank, ncclAllReduce from C++
-    rc = subprocess.run([sys.executable, bench, "--steps", "300", "--warmup", "70", "--no-cpu-baseline", "--rccl-one-rank"],
+    rc = subprocess.run([sys.executable, bench, "--full", "--steps", "300", "--warmup", "70", "--no-cpu-baseline", "--rccl-one-rank"],
                         capture_output=True, text=True, env=env, timeout=600)
     assert rc.returncode == 0, rc.stderr[-2000:]
     assert len(rc.stdout.strip().splitlines()) == 1, rc.stdout     # RCCL's own banner must not land on stdout
@@ -555,7 +597,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(tmp_path):
     rd = json.loads(dup.stdout.strip())
     assert rd["value"] is None and "ncclCommInitRank" in rd["error"] and rd["n_gpus"] == 2
     # the same plain invocation with the test transport asked for: a result line with n_gpus 2
-    own = subprocess.run([sys.executable, bench, "--gpus", "2", "--no-cpu-baseline", "--quick", "--steps", "20", "--warmup", "5",
+    own = subprocess.run([sys.executable, bench, "--gpus", "2", "--full", "--no-cpu-baseline", "--quick", "--steps", "20", "--warmup", "5",
                           "--backend", "gloo"], capture_output=True, text=True, env=env_plain, timeout=900)
     assert own.returncode == 0, own.stderr[-3000:]
     assert len(own.stdout.strip().splitlines()) == 1, own.stdout
@@ -563,7 +605,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(tmp_path):
     assert ro["n_gpus"] == 2 and ro["rccl_ranks_seen"] == 0 and "gloo" in ro["exchange"] and ro["value"] > 0
     assert "(interleaved)" in ro["config"]["parallelism"] and ro["multi_gpu"]["launches_per_exchange"] == 2   # the defaults
     # ... and the ranks it starts get EVERY flag as given (spawn_ranks forwards sys.argv[1:]): partition and group size
-    fwd = subprocess.run([sys.executable, bench, "--gpus", "2", "--no-cpu-baseline", "--quick", "--steps", "300", "--warmup", "70",
+    fwd = subprocess.run([sys.executable, bench, "--gpus", "2", "--full", "--no-cpu-baseline", "--quick", "--steps", "300", "--warmup", "70",
                           "--backend", "gloo", "--partition", "contiguous", "--group", "3", "--batch", "16"],
                          capture_output=True, text=True, env=env_plain, timeout=900)
     assert fwd.returncode == 0, fwd.stderr[-3000:]
@@ -581,7 +623,7 @@ def test_bench_multi_rank_code_path_on_one_gpu(tmp_path):
                                (29520, 4, ["--steps", "700", "--warmup", "70"])):
         two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                               "--master-addr", "127.0.0.1", "--master-port", str(port), bench,
-                              "--gpus", str(world), "--no-cpu-baseline", "--backend", "gloo"] + extra,
+                              "--gpus", str(world), "--full", "--no-cpu-baseline", "--backend", "gloo"] + extra,
                              capture_output=True, text=True, env=env, timeout=900)
         assert two.returncode == 0, two.stderr[-3000:]
         line = [l for l in two.stdout.strip().splitlines() if l.startswith("{")][-1]

@@ -13,6 +13,6 @@ for lib in default ilp; do
 done
 for lib in default ilp default ilp; do
   echo "== bench config B, $lib" >> $O
-  if [ $lib = default ]; then python bench.py --config B --quick --no-cpu-baseline --no-flash 2>/dev/null | python tools/bench_summary.py /dev/stdin 2>/dev/null | head -3 >> $O; else NID_HIP_LIB=$PWD/exp/libnid_ilp.so python bench.py --config B --quick --no-cpu-baseline --no-flash 2>/dev/null | python tools/bench_summary.py /dev/stdin 2>/dev/null | head -3 >> $O; fi
+  if [ $lib = default ]; then python bench.py --full --config B --quick --no-cpu-baseline --no-flash 2>/dev/null | python tools/bench_summary.py /dev/stdin 2>/dev/null | head -3 >> $O; else NID_HIP_LIB=$PWD/exp/libnid_ilp.so python bench.py --full --config B --quick --no-cpu-baseline --no-flash 2>/dev/null | python tools/bench_summary.py /dev/stdin 2>/dev/null | head -3 >> $O; fi
 done
 cat $O

@@ -1,10 +1,11 @@
 #!/bin/bash
 # tools/pmc_round.sh TAG [A|B] [POSES] [BINS] [flash] : SQ / TA / TCP / TCC counter passes over tools/pmc_run.py (POSES-pose launches of the hot
 # kernel -- default 256, the bench's launch size --, one at a time), a few counters per pass (counters only: no trace domains next to --pmc).
-# Raw output -> gpurun_out/TAG_pmc/passN; table -> gpurun_out/TAG_pmc/table.txt (tools/pmc_table.py).
+# Raw output -> $NID_OUT/TAG_pmc/passN; table -> $NID_OUT/TAG_pmc/table.txt (tools/pmc_table.py; NID_OUT defaults to out/).
 tag=$1; cfg=${2:-A}; ppl=${3:-256}; bins=${4:-8}; data=${5:-}
 R=$(pwd)
-O=$R/gpurun_out/${tag}_pmc
+NID_OUT=$(realpath -m "${NID_OUT:-out}")
+O=$NID_OUT/${tag}_pmc
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 i=0
