@@ -100,8 +100,11 @@ int nid_set_href_nan_markers(nid_ctx *ctx, int on);
 int nid_set_stream(nid_ctx *ctx, void *hip_stream);
 /* Threads per workgroup of the evaluation kernel (one workgroup per cell and pose): 128, 256, 512 or 1024.
  * jac_threads: cost + Jacobian launches; 0 = 128, the throughput shape.  The six Jacobian sums depend on the
- * shape in their last bits, so every launch of a context uses the same one.  A blocking caller that evaluates
- * one pose at a time (an LM loop) wants 1024: a cell's pixels in two rounds instead of ten.
+ * shape in their last bits, so every launch of a context uses the same one.  (A cell whose histogram fold needs the
+ * REPAIR pass -- nid_debug_repair_count -- is redone with 256 threads behind a 128-thread launch, but in the launch's
+ * own shape by a diagnostic one (pixel dump, stamps): its Jacobian sums differ between the two in the last bits.)
+ * A blocking caller that evaluates one pose at a time (an LM loop) wants 1024: a cell's pixels in two rounds
+ * instead of ten.
  * cost_threads: cost-only launches; 0 = chosen per launch by its size (their results are the same bits in every
  * shape).  NID_ERR_UNSUPPORTED for any other value.
  * The 512 / 1024 shapes exist for launches of up to 16 poses (they are latency shapes).  A launch of MORE than 16

@@ -22,9 +22,6 @@
 
 #include "nid/nid_c.h"
 #include "nid_eval_launch.h"
-#ifndef NID_REPAIR_NT
-#define NID_REPAIR_NT 256  // (nid_eval_tu.inc)
-#endif
 #include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
 
@@ -262,7 +259,7 @@ void set_hist_params(EvalParams &P) {
 
 // nb_spec: the bin count the kernel is specialised for (its template's NB; 0 = a generic kernel): eval_hist_copies
 size_t eval_lds_bytes(const Geometry &g, int nt, bool resident = false, int nb_spec = -1) {
-  if (nb_spec < 0) nb_spec = (g.nb == 8 || g.nb == 10) ? g.nb : 0;
+  if (nb_spec < 0) nb_spec = nid::nb_spec(g.nb);
   const int nbins = g.nb * g.nb + g.nb;
   // copies + fine levels (the Jacobian block sum of the throughput shapes reuses the area: at least kXposeDoubles); tab + term
   // clamped samples: coarse copies, fine levels, folded sums, flags; near-saturated samples: folded sums, and their bins
@@ -294,7 +291,7 @@ int pick_threads(const nid_ctx *ctx, bool jac, int batch) {
   return nt;
 }
 
-int launch_eval2(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int batch, hipEvent_t eval_end = nullptr) {
+int launch_eval2(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int batch = 1, hipEvent_t eval_end = nullptr) {
   { int rc = resident_quiesce(ctx); if (rc) return rc; }
   P.batch = batch;
   // Workgroup shape of the throughput path: 128 threads.  Measured on MI355X (16 poses per launch, two launches in
@@ -312,7 +309,8 @@ int launch_eval2(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int 
   const bool strict = ctx->math_mode == NID_MATH_STRICT;
   // The kernels live in one translation unit per workgroup shape and kind (nid_eval_launch.h).  Families: the latency
   // form (512 / 1024 threads, FAST math, <= kMaxBatch poses, LAT rounds cover the cell) with or without phase stamps;
-  // diagnostics (128 / 256 threads: they keep the workgroup shape, the Jacobian sums depend on it in their last bits);
+  // diagnostics (128 / 256 threads: the launch's shape, repairs included -- the loop form repairs a 128-thread launch's
+  // queued cells with kRepairThreads threads, whose Jacobian sums differ from the diagnostics' in their last bits);
   // cells of more than 32 * NT slots (test geometries: a single cell of 6 144 / 19 200 pixels: the FAST kernels' BIG
   // instantiation, generic bin count only); everything else the loop form.
   P.repair_queue = ctx->repair_queue_dev[(stream == ctx->aux_stream && !ctx->external_stream) ? 1 : 0];
@@ -320,19 +318,15 @@ int launch_eval2(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int 
   if (stamps_lat) family = kFamStampsLat;
   else if (dbg) family = kFamDbg;
   else if (!strict && P.g.pstride > 32 * nt) family = kFamBig;
-  else if (nt >= 512) {
-    static const bool no_lat = getenv("NID_NO_LAT") != nullptr;  // experiments: the loop form at the latency shapes
-    if (!strict && !no_lat && !ctx->loop_form && P.g.pstride <= lat_rounds(nt) * nt) family = kFamLat;
-  }
+  else if (nt >= 512 && !strict && !ctx->loop_form && P.g.pstride <= lat_rounds(nt) * nt) family = kFamLat;
   if (family == kFamLat && batch > kMaxBatch) return NID_ERR_INVALID_ARG;
   // (the bin-specialised kernels -- the loop and latency families at 8 / 10 bins -- may keep fewer histogram copies than the
   // generic ones the other families run: eval_hist_copies)
-  const int nb_spec = (family == kFamLoop || family == kFamLat) && (P.g.nb == 8 || P.g.nb == 10) ? P.g.nb : 0;
-  size_t lds = eval_lds_bytes(P.g, nt, false, nb_spec);
+  const int nb = family == kFamLoop || family == kFamLat ? nb_spec(P.g.nb) : 0;
+  const size_t lds = eval_lds_bytes(P.g, nt, false, nb);
   if (lds > 160 * 1024) return NID_ERR_UNSUPPORTED;
-  static const char *pad_env = getenv("NID_OCCUPANCY_LDS_PAD");  // occupancy experiments: pad the LDS request
-  if (pad_env) lds = std::min<size_t>(160 * 1024, lds + (size_t)atoi(pad_env));
-  const size_t lds_repair = eval_lds_bytes(P.g, std::max(nt, NID_REPAIR_NT), false, nb_spec);  // k_repair's workgroup shape: nid_eval_tu.inc
+  const size_t lds_repair = eval_lds_bytes(P.g, repair_threads(nt), false, nb);  // k_repair's, behind the loop form
+  if (family == kFamLoop && lds_repair > 160 * 1024) { ctx->last_error = "k_repair needs more than 160 KB of LDS"; return NID_ERR_UNSUPPORTED; }
   switch (nt) {
     case 128: (jac ? launch_eval_128_jac : launch_eval_128_cost)(P, family, strict, lds, lds_repair, stream, batch, eval_end); break;
     case 256: (jac ? launch_eval_256_jac : launch_eval_256_cost)(P, family, strict, lds, lds_repair, stream, batch, eval_end); break;
@@ -341,10 +335,6 @@ int launch_eval2(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int 
   }
   NID_HIP(ctx, hipGetLastError());
   return NID_OK;
-}
-
-int launch_eval(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int batch = 1, hipEvent_t eval_end = nullptr) {
-  return launch_eval2(ctx, P, jac, stream, batch, eval_end);
 }
 
 void fill_common_params(nid_ctx *ctx, double delta, EvalParams *P) {
@@ -805,7 +795,7 @@ int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double d
   S.timed = ctx->timing;
   if (S.timed) { rc = timing_events(ctx, S); if (rc) return rc; }
   if (S.timed) NID_HIP(ctx, hipEventRecord(S.e0, st));
-  rc = launch_eval(ctx, P, want_jac != 0, st, 1, S.timed ? S.e1 : nullptr);  // (timed: e1 right behind k_eval2, in front of k_repair)
+  rc = launch_eval2(ctx, P, want_jac != 0, st, 1, S.timed ? S.e1 : nullptr);  // (timed: e1 right behind k_eval2, in front of k_repair)
   if (rc) return rc;
   if (S.external_target) NID_HIP(ctx, hipEventRecord(S.done, st));
   S.done_slot = slot;
@@ -889,7 +879,7 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   S0.timed = ctx->timing;
   if (S0.timed) { rc = timing_events(ctx, S0); if (rc) return rc; }
   if (S0.timed) NID_HIP(ctx, hipEventRecord(S0.e0, st));
-  rc = launch_eval(ctx, P, want_jac != 0, st, n, S0.timed ? S0.e1 : nullptr);  // (timed: e1 right behind k_eval2, in front of k_repair)
+  rc = launch_eval2(ctx, P, want_jac != 0, st, n, S0.timed ? S0.e1 : nullptr);  // (timed: e1 right behind k_eval2, in front of k_repair)
   if (rc) return rc;
   if (ring >= 0) {
     NID_HIP(ctx, hipEventRecord(ctx->ext_done[ring], st));
@@ -1013,7 +1003,7 @@ int evaluate_common(nid_ctx *ctx, const Pose &pose, int want_jac, double *Ht, do
     NID_HIP(ctx, hipMemsetAsync(ctx->dbg_jc, 0xFF, N * 4, ctx->stream));
   }
   if (!S.resident) {
-    rc = launch_eval(ctx, P, want_jac != 0, ctx->stream);
+    rc = launch_eval2(ctx, P, want_jac != 0, ctx->stream);
     if (rc) return rc;
   }
   rc = direct ? wait_direct_cellout(ctx, S) : wait_host_seq(ctx, S);
@@ -1271,10 +1261,6 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   // 32-bit byte offsets into the reference weights (load_tile_w): 4 x 8 B x nloc x pstride < 2^32
   if ((size_t)g.nloc * (size_t)g.pstride >= ((size_t)1 << 27)) { delete ctx; return NID_ERR_UNSUPPORTED; }
   if (g.nloc >= (1 << 16)) { delete ctx; return NID_ERR_UNSUPPORTED; }  // a repair-queue entry is pose << 16 | cell (k_repair)
-  if (const char *bt = getenv("NID_BLOCK_THREADS")) {  // tuning: both kinds of launches
-    const int v = atoi(bt);
-    if (v == 128 || v == 256 || v == 512 || v == 1024) ctx->jac_threads = ctx->cost_threads = v;
-  }
   auto fail = [&](int rc) { nid_destroy(ctx); return rc; };
   if (hipSetDevice(cfg->device) != hipSuccess) return fail(NID_ERR_NO_DEVICE);
   if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(NID_ERR_HIP);

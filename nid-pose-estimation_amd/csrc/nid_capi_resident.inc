@@ -266,5 +266,5 @@ int resident_fallback(nid_ctx *ctx, Slot &S) {
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   S.resident = false;  // from here on the wait is an ordinary DIRECT wait
   R.pending_slot = -1;
-  return launch_eval(ctx, P, R.jac, ctx->stream);
+  return launch_eval2(ctx, P, R.jac, ctx->stream);
 }

@@ -7,19 +7,9 @@ namespace {
 
 constexpr int NT = NID_TU_NT;
 constexpr bool JAC = NID_TU_JAC != 0;
+constexpr int RNT = repair_threads(NT);
 
 inline dim3 eval_grid(const EvalParams &P, int batch) { return dim3((unsigned)(((P.g.nloc + 7) / 8) * 8 * batch)); }
-
-// k_repair's workgroup shape (round 6): a queued cell is done again from the start by ONE workgroup at one or two waves per
-// SIMD -- nothing hides the latency of its dependent loads, so its time is its number of rounds: the 128-thread launches'
-// repairs run with NID_REPAIR_NT (256) threads, five rounds of a 1200-pixel cell instead of ten (flash pair: 516 queued
-// cells behind a 256-pose launch, profiles/r06_flash_ab.txt).  The six Jacobian sums of a repaired cell
-// are then added up in that shape's order: within 1e-15 of the launch shape's, not its bits (what every other cell, and
-// every repaired cell's entropies and chi2, keep).
-#ifndef NID_REPAIR_NT
-#define NID_REPAIR_NT 256
-#endif
-constexpr int RNT = NT < NID_REPAIR_NT ? NID_REPAIR_NT : NT;
 // k_repair's grid: what fills the chip once at its two waves per SIMD, never more than the launch itself has
 inline dim3 repair_grid(const EvalParams &P, int batch) {
   const unsigned launch = (unsigned)P.g.nloc * (unsigned)batch;
@@ -27,34 +17,28 @@ inline dim3 repair_grid(const EvalParams &P, int batch) {
   return dim3(launch < fill ? launch : fill);
 }
 
-// the loop form: bin-specialised or generic, FAST or STRICT, records in the kernel arguments or (EXT) in device memory;
-// behind it, on the same stream, the kernel that does what it left in the repair queue (k_repair; usually nothing)
-template <int NB>
+// f(NB, STRICT, EXT) for a loop-form launch: bin-specialised or generic, FAST or STRICT, records in the kernel arguments or
+// (EXT: more than kMaxBatch poses, 128 / 256 threads) in device memory
+template <class F>
+void with_loop_kernel(const EvalParams &P, bool strict, F &&f) {
+  with_nb_spec(P.g.nb, [&](auto nb) {
+    auto placed = [&](auto ext) {
+      if (strict) f(nb, std::true_type(), ext);
+      else f(nb, std::false_type(), ext);
+    };
+    if constexpr (NT <= 256) { if (P.slots_ext) return placed(std::true_type()); }
+    placed(std::false_type());
+  });
+}
+
+// the loop form, and behind it on the same stream the kernel that does what it left in the repair queue (k_repair; usually nothing)
 void launch_loop(const EvalParams &P, bool strict, size_t lds, size_t lds_repair, hipStream_t s, int batch, hipEvent_t eval_end) {
-  const dim3 grid = eval_grid(P, batch), block(NT), rgrid = repair_grid(P, batch), rblock(RNT);
-  if constexpr (NT <= 256) {
-    if (P.slots_ext) {  // more than kMaxBatch poses: per-pose records in device memory
-      if (strict) {
-        hipLaunchKernelGGL((k_eval2<NT, JAC, true, NB, false, true>), grid, block, lds, s, P);
-        if (eval_end) (void)hipEventRecord(eval_end, s);
-        hipLaunchKernelGGL((k_repair<RNT, JAC, true, NB, true>), rgrid, rblock, lds_repair, s, P);
-      } else {
-        hipLaunchKernelGGL((k_eval2<NT, JAC, false, NB, false, true>), grid, block, lds, s, P);
-        if (eval_end) (void)hipEventRecord(eval_end, s);
-        hipLaunchKernelGGL((k_repair<RNT, JAC, false, NB, true>), rgrid, rblock, lds_repair, s, P);
-      }
-      return;
-    }
-  }
-  if (strict) {
-    hipLaunchKernelGGL((k_eval2<NT, JAC, true, NB, false>), grid, block, lds, s, P);
+  with_loop_kernel(P, strict, [&](auto nb, auto st, auto ext) {
+    hipLaunchKernelGGL((k_eval2<NT, JAC, st, nb, false, ext>), eval_grid(P, batch), dim3(NT), lds, s, P);
     if (eval_end) (void)hipEventRecord(eval_end, s);
-    hipLaunchKernelGGL((k_repair<RNT, JAC, true, NB, false>), rgrid, rblock, lds_repair, s, P);
-  } else {
-    hipLaunchKernelGGL((k_eval2<NT, JAC, false, NB, false>), grid, block, lds, s, P);
-    if (eval_end) (void)hipEventRecord(eval_end, s);
-    hipLaunchKernelGGL((k_repair<RNT, JAC, false, NB, false>), rgrid, rblock, lds_repair, s, P);
-  }
+    if constexpr (NT == kRepairThreads) (JAC ? launch_repair_jac : launch_repair_cost)(P, strict, lds_repair, s, batch);
+    else hipLaunchKernelGGL((k_repair<RNT, JAC, st, nb, ext>), repair_grid(P, batch), dim3(RNT), lds_repair, s, P);
+  });
 }
 
 }  // namespace
@@ -63,19 +47,20 @@ void launch_loop(const EvalParams &P, bool strict, size_t lds, size_t lds_repair
 #define NID_TU_NAME(nt, kind) NID_TU_NAME2(nt, kind)
 #if NID_TU_JAC
 #define NID_TU_KIND jac
+#define NID_TU_REPAIR launch_repair_jac
 #else
 #define NID_TU_KIND cost
+#define NID_TU_REPAIR launch_repair_cost
 #endif
 
 void NID_TU_NAME(NID_TU_NT, NID_TU_KIND)(const EvalParams &P, int family, bool strict, size_t lds, size_t lds_repair, hipStream_t s, int batch, hipEvent_t eval_end) {
   const dim3 grid = eval_grid(P, batch), block(NT);
+  constexpr int LAT = NT == 512 ? 3 : 2;
   switch (family) {
     case kFamLoop:
-      if (P.g.nb == 8) launch_loop<8>(P, strict, lds, lds_repair, s, batch, eval_end);
-      else if (P.g.nb == 10) launch_loop<10>(P, strict, lds, lds_repair, s, batch, eval_end);
-      else launch_loop<0>(P, strict, lds, lds_repair, s, batch, eval_end);
+      launch_loop(P, strict, lds, lds_repair, s, batch, eval_end);
       return;  // (eval_end recorded in front of k_repair)
-    case kFamDbg:  // diagnostics keep the workgroup shape: the Jacobian sums depend on it in their last bits
+    case kFamDbg:  // the loop form's kernel of this shape with the diagnostics compiled in; it repairs inline, in this shape
       if constexpr (NT <= 256) {
         if (strict) hipLaunchKernelGGL((k_eval2<NT, JAC, true, 0, true>), grid, block, lds, s, P);
         else hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, true>), grid, block, lds, s, P);
@@ -83,32 +68,32 @@ void NID_TU_NAME(NID_TU_NT, NID_TU_KIND)(const EvalParams &P, int family, bool s
       break;
     case kFamBig:  // cells of more than 32 * NT slots (test geometries): FAST, generic bin count
       if constexpr (NT <= 256) {
-        if (P.slots_ext) {
-          hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, false, true, 0, true>), grid, block, lds, s, P);
-          break;
-        }
+        if (P.slots_ext) { hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, false, true, 0, true>), grid, block, lds, s, P); break; }
       }
       hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, false, false, 0, true>), grid, block, lds, s, P);
       break;
     case kFamLat:  // the latency form: 512- / 1024-thread workgroups whose LAT rounds cover the cell (FAST)
-      if constexpr (NT >= 512) {
-        constexpr int LAT = NT == 512 ? 3 : 2;
-        if (P.g.nb == 8) hipLaunchKernelGGL((k_eval2<NT, JAC, false, 8, false, false, LAT>), grid, block, lds, s, P);
-        else if (P.g.nb == 10) hipLaunchKernelGGL((k_eval2<NT, JAC, false, 10, false, false, LAT>), grid, block, lds, s, P);
-        else hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, false, false, LAT>), grid, block, lds, s, P);
-      }
+      if constexpr (NT >= 512)
+        with_nb_spec(P.g.nb, [&](auto nb) { hipLaunchKernelGGL((k_eval2<NT, JAC, false, nb, false, false, LAT>), grid, block, lds, s, P); });
       break;
     case kFamStampsLat:
-      if constexpr (NT >= 512) {
-        constexpr int LAT = NT == 512 ? 3 : 2;
-        hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, true, false, LAT>), grid, block, lds, s, P);
-      }
+      if constexpr (NT >= 512) hipLaunchKernelGGL((k_eval2<NT, JAC, false, 0, true, false, LAT>), grid, block, lds, s, P);
       break;
     default:
       break;
   }
   if (eval_end) (void)hipEventRecord(eval_end, s);  // (these families repair inline: the kernel is the whole launch)
 }
+
+#if NID_TU_NT == 128
+// k_repair<kRepairThreads, ...> of the 128- and 256-thread launches: this unit's code (nid_eval_launch.h)
+static_assert(RNT == kRepairThreads && NT < RNT, "the unit that builds k_repair<kRepairThreads>");
+void NID_TU_REPAIR(const EvalParams &P, bool strict, size_t lds, hipStream_t s, int batch) {
+  with_loop_kernel(P, strict, [&](auto nb, auto st, auto ext) {
+    hipLaunchKernelGGL((k_repair<RNT, JAC, st, nb, ext>), repair_grid(P, batch), dim3(RNT), lds, s, P);
+  });
+}
+#endif
 
 }  // namespace nid
 

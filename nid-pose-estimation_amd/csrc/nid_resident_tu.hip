@@ -13,19 +13,12 @@ void launch_res(const EvalParams &P, size_t lds, unsigned grid, hipStream_t s, c
   (void)hipGetLastError();
   hipLaunchKernelGGL((k_resident<NT, NB, LAT>), dim3(grid), dim3(NT), lds, s, P, ctl, word0, idle_ticks, xform_mode);
 }
-template <int NT, int LAT>
-void launch_res_nb(const EvalParams &P, size_t lds, unsigned grid, hipStream_t s, const ResidentCtl *ctl, unsigned long long word0,
-                   long long idle_ticks, int xform_mode) {
-  if (P.g.nb == 8) launch_res<NT, 8, LAT>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode);
-  else if (P.g.nb == 10) launch_res<NT, 10, LAT>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode);
-  else launch_res<NT, 0, LAT>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode);
-}
 }  // namespace
 
 void launch_resident(const EvalParams &P, int nt, size_t lds, unsigned grid, hipStream_t s, const ResidentCtl *ctl,
                      unsigned long long word0, long long idle_ticks, int xform_mode) {
-  if (nt == 512) launch_res_nb<512, 3>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode);
-  else launch_res_nb<256, 0>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode);
+  if (nt == 512) with_nb_spec(P.g.nb, [&](auto nb) { launch_res<512, nb, 3>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode); });
+  else with_nb_spec(P.g.nb, [&](auto nb) { launch_res<256, nb, 0>(P, lds, grid, s, ctl, word0, idle_ticks, xform_mode); });
 }
 
 }  // namespace nid

@@ -124,8 +124,9 @@ def test_multi_cell_ranges_and_argument_checks(capi):
 
 def test_unit_flags_reach_only_the_throughput_unit():
     """csrc/UNIT_FLAGS (round 6): the machine scheduler's max-ilp strategy goes to the 128-thread cost + Jacobian unit and to no
-    other -- the latency units measure slower with it (profiles/r06_sched_strategy_ab.txt).  build() and the variant / register
-    tools read the same file."""
+    other -- the latency units measure slower with it (profiles/r06_sched_strategy_ab.txt).  That unit also builds the
+    Jacobian kind's k_repair<256>, behind the 128- and the 256-thread launches (nid_eval_launch.h).  build() and the variant /
+    register tools parse the file with the same function."""
     import importlib
     import os
     entry = importlib.import_module("__graft_entry__")
@@ -135,3 +136,49 @@ def test_unit_flags_reach_only_the_throughput_unit():
     flagged = {u: entry._unit_flags(u) for u in units}
     assert flagged["nid_eval_nt128_jac.hip"] == ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
     assert all(not f for u, f in flagged.items() if u != "nid_eval_nt128_jac.hip"), flagged
+    launch_h = open(os.path.join(csrc, "nid_eval_launch.h")).read()
+    assert "constexpr int kRepairThreads = 256;" in launch_h
+    assert "#if NID_TU_NT == 128\n" in open(os.path.join(csrc, "nid_eval_tu.inc")).read()  # the unit that builds k_repair<256>
+    for tool in ("build_variant.py", "kernel_regs.py"):
+        assert "from __graft_entry__ import _unit_flags" in open(os.path.join(os.path.dirname(csrc), "..", "tools", tool)).read()
+
+
+def _code_object_kernels(lib_path, tmp_path):
+    """the kernels of every gfx950 code object in the library's .hip_fatbin section: one list per offload bundle (one per
+    translation unit with device code)"""
+    import struct
+    llvm = "/opt/rocm/llvm/bin"
+    fat = tmp_path / "fatbin"
+    subprocess.check_call([f"{llvm}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, str(fat)])
+    data = fat.read_bytes()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    out, start = [], data.find(magic)
+    while start >= 0:
+        (count,) = struct.unpack_from("<Q", data, start + len(magic))
+        pos, end = start + len(magic) + 8, start + len(magic) + 8
+        for _ in range(count):
+            off, size, id_len = struct.unpack_from("<QQQ", data, pos)
+            triple = data[pos + 24:pos + 24 + id_len].decode()
+            pos += 24 + id_len
+            end = max(end, start + off + size)
+            if triple.endswith("gfx950"):
+                co = tmp_path / f"co{len(out)}"
+                co.write_bytes(data[start + off:start + off + size])
+                syms = subprocess.run([f"{llvm}/llvm-readelf", "-sW", str(co)], capture_output=True, text=True, check=True).stdout
+                out.append(sorted(set(re.findall(r"(\S+)\.kd$", syms, re.M))))
+        start = data.find(magic, end)
+    return out
+
+
+def test_every_kernel_is_built_in_one_unit(capi, tmp_path):
+    """Two code objects that define the same kernel register it twice, and the HIP runtime serves one copy to every launch --
+    which one, the order of the modules decides.  The copies can differ (csrc/UNIT_FLAGS), so each kernel is compiled in
+    exactly one translation unit."""
+    units = _code_object_kernels(capi.LIB_PATH, tmp_path)
+    assert len(units) >= 10 and all(units), [len(u) for u in units]
+    seen = {}
+    for i, kernels in enumerate(units):
+        for k in kernels:
+            seen.setdefault(k, []).append(i)
+    twice = sorted(k for k, where in seen.items() if len(where) > 1)
+    assert not twice, f"{len(twice)} kernels in two code objects: {twice[:4]}"

@@ -8,6 +8,8 @@ the translation units whose file name contains A or B only (e.g. --units nt128,n
 import glob, os, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, root)
+from __graft_entry__ import _unit_flags
 args = sys.argv[1:]
 name = args.pop(0)
 src = root
@@ -21,16 +23,10 @@ units = sorted(glob.glob(os.path.join(csrc, "*.hip"))) + [os.path.join(csrc, "ni
 units = [u for u in units if os.path.exists(u)]
 os.makedirs(os.path.join(root, "exp"), exist_ok=True)
 with tempfile.TemporaryDirectory() as d:
-    def unit_flags(u):  # the product's own per-unit flags (csrc/UNIT_FLAGS of the tree that is built; older trees have none)
-        out, path = [], os.path.join(csrc, "UNIT_FLAGS")
-        for line in (open(path) if os.path.exists(path) and not os.environ.get("NID_NO_UNIT_FLAGS") else []):
-            line = line.split("#", 1)[0].strip()
-            if line and line.split(":", 1)[0].strip() in os.path.basename(u):
-                out += line.split(":", 1)[1].split()
-        return out
     def flags(u):
         extra = args if only_units is None or any(k in os.path.basename(u) for k in only_units) else []
-        return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", *unit_flags(u), *extra, "-I", os.path.join(src, "include"), "-I", csrc]
+        unit = [] if os.environ.get("NID_NO_UNIT_FLAGS") else _unit_flags(u, csrc)  # the product's own (of the tree that is built)
+        return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", *unit, *extra, "-I", os.path.join(src, "include"), "-I", csrc]
     jobs = [["/opt/rocm/bin/hipcc"] + flags(u) + ["-c", "-o", os.path.join(d, os.path.basename(u) + ".o"), u] for u in units]
     with ThreadPoolExecutor(min(8, len(jobs))) as pool:
         list(pool.map(subprocess.check_call, jobs))

@@ -6,6 +6,8 @@ contains SUBSTR."""
 import glob, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, root)
+from __graft_entry__ import _unit_flags
 args = sys.argv[1:]
 keep = only = None
 for flag in ("--keep", "--only"):
@@ -21,11 +23,7 @@ with tempfile.TemporaryDirectory() as d:
     os.makedirs(outdir, exist_ok=True)
     def build(u):
         out = os.path.join(outdir, os.path.basename(u)[:-4] + ".s")
-        unit = []  # the product's own per-unit flags (csrc/UNIT_FLAGS)
-        for line in (open(csrc + "/UNIT_FLAGS") if os.path.exists(csrc + "/UNIT_FLAGS") and not os.environ.get("NID_NO_UNIT_FLAGS") else []):
-            line = line.split("#", 1)[0].strip()
-            if line and line.split(":", 1)[0].strip() in os.path.basename(u):
-                unit += line.split(":", 1)[1].split()
+        unit = [] if os.environ.get("NID_NO_UNIT_FLAGS") else _unit_flags(u)  # the product's own per-unit flags (csrc/UNIT_FLAGS)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S",
                                *unit, *args, "-I", root + "/include", "-I", csrc, "-o", out, u], stderr=subprocess.DEVNULL)
         return out
