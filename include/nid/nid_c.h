@@ -271,7 +271,12 @@ int nid_launch_batch_to(nid_ctx *ctx, int first_slot, int n, const double *poses
  * divides NID_SLOTS), min(16, NID_SLOTS/batch) launches in flight on the context's two streams, each
  * launch's result blocks written to a device buffer and brought home by one copy behind it;
  * reduced_out (n x NID_REDUCED_LEN, may be NULL) receives every pose's [chi2, b, H upper, n_active]
- * block.  Blocking. */
+ * block.  Blocking.
+ * `batch` (<= NID_MAX_BATCH) is the unit of the pipeline's bookkeeping and the largest grid of a short
+ * sequence.  A LONG sequence -- at least two grids' worth of poses -- may evaluate several consecutive
+ * batches in one grid (up to 1024 poses, 2 to 4 grids in flight, buffers of the library's own instead of
+ * the slots): fewer launches, record copies and result copies for the same poses, and for every pose the
+ * same bits as in a launch of `batch` poses or alone. */
 int nid_run_sequence(nid_ctx *ctx, const double *poses7, int n, int batch, int want_jac,
                      double huber_delta, double *reduced_out);
 /* A DEPENDENT chain of n evaluations, the way a Gauss-Newton / LM loop issues them: one pose per launch, the host

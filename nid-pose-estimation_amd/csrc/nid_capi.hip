@@ -139,6 +139,16 @@ struct nid_ctx {
   hipEvent_t seq_done[kSeqRing] = {}, seq_fence[kSeqRing] = {};
   size_t seq_cap = 0;
   hipStream_t copy_stream = nullptr;
+  // nid_run_sequence's FUSED grids (several consecutive batches of a long sequence in one grid of up to kSeqGridMax poses):
+  // what each pose of each grid in flight needs besides its result block in seq_dev / seq_host -- per-cell blocks, group
+  // sums, tickets (zero between launches, like the slots') and its argument record.  Private to the pipeline: the public
+  // slots are neither used nor marked pending by a fused sequence.  Made on first use (ensure_seq_pool), freed with the context.
+  struct SeqPool {
+    int grid = 0, depth = 0;  // poses per grid the pool is carved for, grids in flight
+    double *quad = nullptr, *gpart = nullptr;  // [depth][grid][nloc * kQuad], [depth][grid][ngroups * kQuad]
+    unsigned *ticket = nullptr;                // [depth][grid][ticket_words]
+    SlotArgs *rec_dev = nullptr, *rec_host = nullptr;  // [depth][grid]: a grid's records (pinned mirror, one in-stream copy)
+  } pool;
   // what the slots' buffers are carved from (one allocation per kind)
   double *slab_cellout = nullptr, *slab_reduced = nullptr, *slab_quad = nullptr, *slab_gpart = nullptr, *slab_reduced_host = nullptr;
   unsigned *slab_ticket = nullptr;
@@ -151,6 +161,7 @@ void resident_retire(nid_ctx *ctx);  // every call that changes what a resident 
 int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int want_jac, double delta, double *reduced_dev_base = nullptr,
                  bool on_aux_stream = false, bool relaunch_ok = false, bool allow_direct = true);
 int resident_quiesce(nid_ctx *ctx);  // ... and every ordinary evaluation launch (the resident workgroups hold most of every CU)
+void free_seq_pool(nid_ctx *ctx);
 
 #define NID_HIP(ctx, expr)                                                            \
   do {                                                                                \
@@ -1295,7 +1306,7 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   if ((rc = dev_alloc(ctx, &ctx->repair_count_dev, 1))) return fail(rc);
   if (hipMemset(ctx->repair_count_dev, 0, sizeof(unsigned long long)) != hipSuccess) return fail(NID_ERR_HIP);
   for (int q = 0; q < 2; q++) {  // one queue per launch stream: [count | exit ticket | (pose << 16 | cell, repair set x 2) ...], see k_repair
-    const size_t n = 2 + 3 * (size_t)g.nloc * kMaxBatchExt;
+    const size_t n = 2 + 3 * (size_t)g.nloc * kSeqGridMax;  // (one entry per workgroup of the largest grid at most)
     if ((rc = dev_alloc(ctx, &ctx->repair_queue_dev[q], n))) return fail(rc);
     if (hipMemset(ctx->repair_queue_dev[q], 0, n * sizeof(unsigned)) != hipSuccess) return fail(NID_ERR_HIP);
   }
@@ -1381,6 +1392,7 @@ int nid_destroy(nid_ctx *ctx) {
     if (ctx->seq_fence[r]) (void)hipEventDestroy(ctx->seq_fence[r]);
   }
   if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
+  free_seq_pool(ctx);
   (void)hipFree(ctx->slab_cellout); (void)hipFree(ctx->slab_reduced); (void)hipFree(ctx->slab_quad);
   (void)hipFree(ctx->slab_ticket); (void)hipFree(ctx->slab_gpart);
   if (ctx->slab_reduced_host) (void)hipHostFree(ctx->slab_reduced_host);
@@ -1827,6 +1839,98 @@ int ensure_seq_ring(nid_ctx *ctx, int batch) {
   ctx->seq_cap = (size_t)batch;
   return NID_OK;
 }
+
+// ---- fused grids of the pipelined loop ------------------------------------------------------------------------------
+// What a pipelined launch costs besides its evaluation kernel -- the record copy, k_repair, fence and event records, the
+// dispatch gaps, one workgroup's duration of ramp-down and ramp-up -- is paid per launch, not per pose, and a pose gives
+// the same bits alone, in any launch, on either stream.  So a LONG sequence goes as fewer, larger grids: F consecutive
+// batches in one grid, F as large as kSeqGridMax allows.  Such a grid is beyond what the public slots can hold in flight
+// (NID_SLOTS / kSeqGridMax = one), so its poses' buffers come out of a pool of the pipeline's own.
+//
+// kSeqPoolBudget caps the pool's device memory.  Per pose: quad nloc x 32 doubles, gpart ngroups x 32 doubles, tickets,
+// a result block and a record (~0.5 KB together).
+//   config A (640x480, 256 cells, 16 groups): 64 KB + 4 KB + 0.5 KB = 68.5 KB; a 1024-pose grid 68.5 MB; 4 in flight 274 MB
+//   config B (1280x960, 1024 cells, 32 groups): 256 KB + 8 KB + 0.6 KB = 264.6 KB; a 1024-pose grid 264.6 MB; 4 in flight
+//     1058 MB is over, 3 in flight 794 MB
+// (the public slots of config B hold 1024 x (256 KB quad + 80 KB cellout + 8 KB gpart) = 344 MB).  Over budget at two
+// grids in flight, F goes down instead -- to 1, the unfused pipeline, at worst.
+constexpr size_t kSeqPoolBudget = (size_t)1 << 30;
+constexpr int kSeqPoolMinDepth = 2, kSeqPoolMaxDepth = 4;  // grids in flight (two streams: at least one each)
+
+size_t seq_ticket_words(const nid_ctx *ctx) { return ((size_t)ctx->ngroups + 4 + 3) & ~(size_t)3; }  // (a slot's: nid_create)
+
+size_t seq_pool_bytes_per_pose(const nid_ctx *ctx) {
+  return ((size_t)ctx->g.nloc + (size_t)ctx->ngroups + 1) * kQuad * sizeof(double) + seq_ticket_words(ctx) * sizeof(unsigned) + sizeof(SlotArgs);
+}
+
+// batches per grid of a long sequence (1: not fused) and how many such grids are in flight
+int seq_fusion(const nid_ctx *ctx, int batch, int *depth) {
+  int F = std::max(1, kSeqGridMax / batch);
+  const size_t per_pose = seq_pool_bytes_per_pose(ctx);
+  while (F > 1 && (size_t)kSeqPoolMinDepth * F * batch * per_pose > kSeqPoolBudget) F--;
+  *depth = (int)std::min<size_t>(kSeqPoolMaxDepth, std::max<size_t>(kSeqPoolMinDepth, kSeqPoolBudget / ((size_t)F * batch * per_pose)));
+  return F;
+}
+
+void free_seq_pool(nid_ctx *ctx) {
+  nid_ctx::SeqPool &Q = ctx->pool;
+  (void)hipFree(Q.quad); (void)hipFree(Q.gpart); (void)hipFree(Q.ticket); (void)hipFree(Q.rec_dev);
+  if (Q.rec_host) (void)hipHostFree(Q.rec_host);
+  Q = nid_ctx::SeqPool();
+}
+
+// the pool for `depth` grids of `grid` poses in flight (a context's geometry is fixed: what changes between calls is the
+// batch, and with it the grid); the result blocks are the ring's (ensure_seq_ring)
+int ensure_seq_pool(nid_ctx *ctx, int grid, int depth) {
+  nid_ctx::SeqPool &Q = ctx->pool;
+  { int rc = ensure_seq_ring(ctx, grid); if (rc) return rc; }
+  if (Q.grid == grid && Q.depth == depth) return NID_OK;
+  resident_retire(ctx);  // (hipFree waits for the whole device)
+  free_seq_pool(ctx);
+  const size_t poses = (size_t)grid * depth, n_ticket = seq_ticket_words(ctx);
+  int rc;
+  if ((rc = dev_alloc(ctx, &Q.quad, poses * ctx->g.nloc * kQuad))) return rc;
+  if ((rc = dev_alloc(ctx, &Q.gpart, poses * ctx->ngroups * kQuad))) return rc;
+  if ((rc = dev_alloc(ctx, &Q.ticket, poses * n_ticket))) return rc;
+  NID_HIP(ctx, hipMemset(Q.ticket, 0, poses * n_ticket * sizeof(unsigned)));  // (the kernels leave them zero behind every launch)
+  if ((rc = dev_alloc(ctx, &Q.rec_dev, poses))) return rc;
+  if (hipHostMalloc(reinterpret_cast<void **>(&Q.rec_host), poses * sizeof(SlotArgs), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
+  Q.grid = grid;
+  Q.depth = depth;
+  return NID_OK;
+}
+
+// one grid of the fused pipeline: n <= pool.grid poses with pool entry r's buffers, results to seq_dev[r]; one record
+// upload, k_eval2, k_repair (launch_batch's order, without slots)
+int launch_seq_grid(nid_ctx *ctx, int r, int n, const double *poses7, int want_jac, double delta, hipStream_t st) {
+  nid_ctx::SeqPool &Q = ctx->pool;
+  int rc = check_ready(ctx);
+  if (rc) return rc;
+  if (n < 1 || n > Q.grid || r < 0 || r >= Q.depth) return NID_ERR_INVALID_ARG;
+  EvalParams P{};
+  fill_common_params(ctx, delta, &P);
+  const size_t base = (size_t)r * Q.grid, n_quad = (size_t)ctx->g.nloc * kQuad, n_gpart = (size_t)ctx->ngroups * kQuad, n_ticket = seq_ticket_words(ctx);
+  // (the ragged end of a sequence may be <= kMaxBatch poses: records in the kernel arguments, like every such launch)
+  SlotArgs *recs = n > kMaxBatch ? Q.rec_host + base : P.slot;
+  for (int k = 0; k < n; k++) {
+    SlotArgs &A = recs[k];
+    pose_from_pose7(poses7 + 7 * (size_t)k, ctx->xform, &A.pose);
+    A.cellout = nullptr;  // nobody reads the per-cell outputs of such a launch
+    A.quad = Q.quad + (base + k) * n_quad;
+    A.gpart = Q.gpart + (base + k) * n_gpart;
+    A.ticket = Q.ticket + (base + k) * n_ticket;
+    A.out_reduced = ctx->seq_dev[r] + (size_t)k * kReducedLen;
+    A.host_seq = nullptr;  // (the result is on the device: the copy behind the launch and its event say when it is home)
+    A.launch_seq = 0;
+    A.cellout_host = 0;
+    A.host_quad = 0;
+  }
+  if (n > kMaxBatch) {
+    P.slots_ext = Q.rec_dev + base;
+    NID_HIP(ctx, hipMemcpyAsync(Q.rec_dev + base, recs, (size_t)n * sizeof(SlotArgs), hipMemcpyHostToDevice, st));
+  }
+  return launch_eval2(ctx, P, want_jac != 0, st, n);
+}
 }  // namespace
 
 extern "C" {
@@ -1839,6 +1943,11 @@ int nid_run_sequence(nid_ctx *ctx, const double *poses7, int n, int batch, int w
   // lowest latency; for a stream of launches that is 256 system-scope fences and PCIe writes per launch from
   // inside the kernel: this form measured 254 k -> 270-280 k evaluations/s on 640x480.)
   // (any batch <= NID_MAX_BATCH: ring entry r owns the slots r * batch .. r * batch + batch - 1, and depth * batch <= NID_SLOTS below)
+  // LONG sequences -- n >= 2 F batch, F = kSeqGridMax / batch unless the pool's budget lowers it (seq_fusion) -- go as
+  // grids of F consecutive batches: one record upload, one k_eval2 grid of F * batch poses, one k_repair, one fence and one
+  // result copy per grid instead of per batch, the last grid taking what remains (whole batches and a ragged end); 2 to 4
+  // grids in flight with buffers from the context's private pool.  `batch` stays the largest grid of shorter sequences and
+  // the unit all of this is counted in; a pose's bits do not depend on the grid it went in.
   if (!ctx || !poses7 || n < 0 || batch < 1 || batch > kMaxBatchExt) return NID_ERR_INVALID_ARG;
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
@@ -1858,31 +1967,45 @@ int nid_run_sequence(nid_ctx *ctx, const double *poses7, int n, int batch, int w
     }
     return NID_OK;
   }
-  const int depth = std::min((int)nid_ctx::kSeqRing, NID_SLOTS / batch);
-  { int rc = ensure_seq_ring(ctx, batch); if (rc) return rc; }
+  // (timed and diagnostic launches are per slot: such contexts keep the unfused form)
+  int pool_depth = 0;
+  const int F = (ctx->timing || ctx->dbg_enabled || ctx->dbg_stamps) ? 1 : seq_fusion(ctx, batch, &pool_depth);
+  const bool fused = F > 1 && (long)n >= 2L * F * batch;
+  const int unit = fused ? F * batch : batch;  // poses per grid
+  const int depth = fused ? pool_depth : std::min((int)nid_ctx::kSeqRing, NID_SLOTS / batch);
+  { int rc = fused ? ensure_seq_pool(ctx, unit, depth) : ensure_seq_ring(ctx, batch); if (rc) return rc; }
   // Consecutive launches alternate between the context's two streams: a launch's last workgroups leave most CUs
-  // idle for a while and the next launch's workgroups fill that tail.  Launches are independent (own slots, own
-  // result buffers), so no cross-stream ordering is needed.
+  // idle for a while and the next launch's workgroups fill that tail.  Launches are independent (own slots or pool
+  // entries, own result buffers), so no cross-stream ordering is needed.
   static const bool one_stream = getenv("NID_ONE_STREAM") != nullptr;
-  Pose p[kMaxBatchExt];
-  const int launches = (n + batch - 1) / batch;
+  Pose p[kMaxBatchExt];  // (the unfused form's; a fused grid's poses go straight into its records)
+  const int launches = (n + unit - 1) / unit;
   auto collect = [&](int l) -> int {  // launch l has landed in seq_host[l % depth]
     const int r = l % depth;
     NID_HIP(ctx, hipEventSynchronize(ctx->seq_done[r]));
-    const int first = l * batch, cnt = std::min(batch, n - first);
+    const int first = l * unit, cnt = std::min(unit, n - first);
     if (reduced_out) std::memcpy(reduced_out + (size_t)first * kReducedLen, ctx->seq_host[r], (size_t)cnt * kReducedLen * sizeof(double));
-    for (int k = 0; k < cnt; k++) ctx->slots[r * batch + k].pending = false;
+    if (!fused) for (int k = 0; k < cnt; k++) ctx->slots[r * batch + k].pending = false;
     return NID_OK;
   };
   for (int l = 0; l < launches; l++) {
     const int r = l % depth;
-    if (l >= depth) { int rc = collect(l - depth); if (rc) return rc; }  // frees ring entry r and its slots
-    const int first = l * batch, nb = std::min(batch, n - first);
-    for (int k = 0; k < nb; k++) pose_from_pose7(poses7 + 7 * (size_t)(first + k), ctx->xform, &p[k]);
+    if (l >= depth) { int rc = collect(l - depth); if (rc) return rc; }  // frees ring entry r and its slots / pool entry
+    const int first = l * unit, nb = std::min(unit, n - first);
     const bool aux = !one_stream && (l & 1) && !ctx->external_stream;
-    int rc = launch_batch(ctx, r * batch, nb, p, want_jac, delta, ctx->seq_dev[r], aux);
-    if (rc) return rc;
     hipStream_t ls = aux ? ctx->aux_stream : ctx->stream;
+    int rc;
+    if (fused) {
+      rc = launch_seq_grid(ctx, r, nb, poses7 + 7 * (size_t)first, want_jac, delta, ls);
+      if (rc) {  // no slot says that pool entries are still in use: let the grids that did go out finish
+        (void)hipStreamSynchronize(ctx->stream);
+        if (!ctx->external_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamSynchronize(ctx->copy_stream); }
+      }
+    } else {
+      for (int k = 0; k < nb; k++) pose_from_pose7(poses7 + 7 * (size_t)(first + k), ctx->xform, &p[k]);
+      rc = launch_batch(ctx, r * batch, nb, p, want_jac, delta, ctx->seq_dev[r], aux);
+    }
+    if (rc) return rc;
     hipStream_t cs = ctx->external_stream ? ctx->stream : ctx->copy_stream;
     if (cs != ls) {
       NID_HIP(ctx, hipEventRecord(ctx->seq_fence[r], ls));

@@ -92,6 +92,10 @@ struct Tiles {
 
 constexpr int kMaxBatch = 16;     // candidate poses of one launch whose arguments ride in the kernel arguments
 constexpr int kMaxBatchExt = 256;  // ... or, beyond that, in a device-resident SlotArgs array (EvalParams::slots_ext)
+// The most poses of ONE grid: nid_run_sequence's pipeline evaluates several consecutive batches of a long sequence in one
+// grid of up to this many poses (internal; every public launch call stays within kMaxBatchExt).  Sizes the repair queues.
+constexpr int kSeqGridMax = 1024;
+static_assert(kSeqGridMax >= kMaxBatchExt && kSeqGridMax <= (1 << 16), "a repair-queue entry is pose << 16 | cell");
 // FAST math mode: per span 4 basis functions x (4 value + 3 derivative) polynomial coefficients in
 // t = u - floor(u):  B_k = ((a3 t + a2) t + a1) t + a0,  B_k' = (d2 t + d1) t + d0
 constexpr int kCoefRow = 28;
@@ -2201,7 +2205,7 @@ __device__ __forceinline__ bool eval_cell(const EvalParams &P, const SlotArgs &S
         const unsigned i = __hip_atomic_fetch_add(q, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // (a launch pushes at most one entry per workgroup and k_repair empties the queue behind it: the bound only
         // holds against a queue that was never drained)
-        if (i < (unsigned)P.g.nloc * (unsigned)kMaxBatchExt) {  // the entry: which cell and pose, and the repair set the fold found
+        if (i < (unsigned)P.g.nloc * (unsigned)kSeqGridMax) {  // the entry: which cell and pose, and the repair set the fold found
           const uint2 rs = *reinterpret_cast<const uint2 *>(repair_set);
           q[2 + 3 * i] = ((unsigned)pose_idx << 16) | (unsigned)cl;
           q[3 + 3 * i] = rs.x;
