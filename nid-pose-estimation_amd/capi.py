@@ -49,6 +49,30 @@ SYMBOLS = [
     "nid_contract_bytes", "nid_debug_repair_count", "nid_set_short_sequence_policy",
 ]
 
+# include/nid/nid_multistart.h (a header of its own: the symbols above are nid_c.h's, pinned by tests/test_abi.py)
+MULTISTART_SYMBOLS = ["nid_multistart_lm", "nid_lm_step_host"]
+MS_RUNNING, MS_ITERATIONS, MS_TRIALS_EXHAUSTED, MS_RHO_NOT_NEGATIVE, MS_NBAD = 0, 1, 2, 3, 4
+MS_F_FIRST, MS_F_ACCEPT, MS_F_REJECT, MS_F_OUTER_END, MS_F_SOLVE_FAILED, MS_F_FINISHED = 1, 2, 4, 8, 16, 32
+
+
+class MsState(C.Structure):
+    """nid_ms_state: one LM chain (zero it, set pose7 / iterations / xform_mode: new_ms_state)."""
+    _fields_ = [("pose7", C.c_double * 7), ("chi2", C.c_double), ("H", C.c_double * 21), ("b", C.c_double * 6),
+                ("lambda_", C.c_double), ("ni", C.c_double), ("ini_chi2", C.c_double), ("x", C.c_double * 6),
+                ("trial7", C.c_double * 7), ("trial_chi2", C.c_double), ("rho", C.c_double),
+                ("rec_q", C.c_double * 7), ("rec_M", C.c_double * 12),
+                ("iterations", C.c_int32), ("xform_mode", C.c_int32), ("started", C.c_int32), ("n_active", C.c_int32),
+                ("n_bad", C.c_int32), ("trials", C.c_int32), ("outer_done", C.c_int32), ("trials_total", C.c_int32),
+                ("solve_ok", C.c_int32), ("status", C.c_int32), ("flags", C.c_int32), ("rec_mode", C.c_int32)]
+
+
+# nid_ms_result / nid_ms_trace as numpy records (tobytes() of two arrays compares every bit)
+MS_RESULT_DTYPE = np.dtype([("pose7", "f8", 7), ("chi2", "f8"), ("lambda_", "f8"), ("n_active", "i4"),
+                            ("outer_iterations", "i4"), ("trials", "i4"), ("status", "i4")])
+MS_TRACE_DTYPE = np.dtype([("trial_chi2", "f8"), ("lambda_", "f8"), ("rho", "f8"), ("pose7", "f8", 7),
+                           ("flags", "i4"), ("status", "i4")])
+assert C.sizeof(MsState) == 624 and MS_RESULT_DTYPE.itemsize == 88 and MS_TRACE_DTYPE.itemsize == 88
+
 _lib = None
 
 
@@ -132,6 +156,9 @@ def load():
         lib.nid_set_short_sequence_policy.argtypes = [vp, C.c_int, C.c_int]
     lib.nid_contract_bytes.restype = C.c_int64
     lib.nid_contract_bytes.argtypes = [vp]
+    if hasattr(lib, "nid_multistart_lm"):   # (an older experiment build, NID_HIP_LIB, lacks it: calling it is an error there)
+        lib.nid_multistart_lm.argtypes = [vp, c_dp, C.c_int, C.c_int, C.c_double, C.c_int, vp, c_ip, vp, c_ip]
+        lib.nid_lm_step_host.argtypes = [C.POINTER(MsState), c_dp]
     _lib = lib
     return lib
 
@@ -418,6 +445,24 @@ class Context:
         """How nid_launch_batch / nid_run_sequence split a short sequence (0, 0: the library's table)."""
         self._check(self.lib.nid_set_short_sequence_policy(self.h, int(poses_per_launch), int(streams)), "nid_set_short_sequence_policy")
 
+    def multistart_lm(self, poses, iterations, delta, max_rounds=0, trace=False):
+        """Many LM chains at once, stepped on the device (nid_multistart_lm).  Returns (results, best, rounds_done) or,
+        with trace=True, (results, best, rounds_done, trace): results an MS_RESULT_DTYPE array [n], trace an
+        MS_TRACE_DTYPE array [rounds_done, n]."""
+        p = _d(np.asarray(poses).reshape(-1, 7))
+        n = p.shape[0]
+        cap = int(max_rounds) if max_rounds > 0 else 1 + 10 * int(iterations)
+        res = np.zeros(max(n, 1), dtype=MS_RESULT_DTYPE)
+        tr = np.zeros((cap, max(n, 1)), dtype=MS_TRACE_DTYPE) if trace else None
+        best, rounds = C.c_int32(-2), C.c_int32(0)
+        self._check(self.lib.nid_multistart_lm(self.h, _dp(p), n, int(iterations), float(delta), int(max_rounds),
+                                               res.ctypes.data_as(C.c_void_p), C.byref(best),
+                                               tr.ctypes.data_as(C.c_void_p) if trace else None, C.byref(rounds)),
+                    "nid_multistart_lm")
+        if trace:
+            return res[:n], int(best.value), int(rounds.value), tr[:rounds.value, :n]
+        return res[:n], int(best.value), int(rounds.value)
+
     def repair_count(self, reset=False):
         """(cell, pose) evaluations that ran the fold's repair pass (kLinFlagW in csrc/nid_kernels.hip.h)."""
         if not hasattr(self.lib, "nid_debug_repair_count"):
@@ -458,6 +503,26 @@ def unpack_reduced(r):
     na = C.c_int32(0)
     lib.nid_unpack_reduced(_dp(r), _dp(H), _dp(b), C.byref(chi2), C.byref(na))
     return H.reshape(6, 6), b, chi2.value, na.value
+
+
+def new_ms_state(pose7, iterations, xform=XFORM_QUAT):
+    """A fresh chain for lm_step_host."""
+    st = MsState()
+    st.pose7[:] = [float(v) for v in pose7]
+    st.iterations = int(iterations)
+    st.xform_mode = int(xform)
+    return st
+
+
+def lm_step_host(state, reduced32):
+    """One step of one LM chain on the host (nid_lm_step_host: the function k_lm_step runs, compiled for the host) with
+    the reduced block of the pose the chain asked for.  True while the chain is running."""
+    r = _d(reduced32)
+    assert r.size == NID_REDUCED_LEN
+    rc = load().nid_lm_step_host(C.byref(state), _dp(r))
+    if rc < 0:
+        raise NidError(f"nid_lm_step_host: {rc}")
+    return bool(rc)
 
 
 def log2_fast_host(x):

@@ -21,7 +21,9 @@
 #include <vector>
 
 #include "nid/nid_c.h"
+#include "nid/nid_multistart.h"
 #include "nid_eval_launch.h"
+#include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
 #include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
 
@@ -149,6 +151,19 @@ struct nid_ctx {
     unsigned *ticket = nullptr;                // [depth][grid][ticket_words]
     SlotArgs *rec_dev = nullptr, *rec_host = nullptr;  // [depth][grid]: a grid's records (pinned mirror, one in-stream copy)
   } pool;
+  // nid_multistart_lm's buffers (nid_multistart.inc): per chain what a pose of a grid needs -- per-cell blocks, group sums,
+  // zeroed tickets, its record, its result block -- and the chain's state; per round one word (chains still running) and,
+  // when asked for, the trace.  Private to that call, grow only, freed with the context.
+  struct MsPool {
+    int chains = 0, rounds = 0;
+    double *quad = nullptr, *gpart = nullptr, *reduced = nullptr;
+    unsigned *ticket = nullptr, *running_dev = nullptr, *running_host = nullptr;  // (running_host: pinned)
+    SlotArgs *rec_dev = nullptr;
+    nid_ms_state *state_dev = nullptr;
+    nid_ms_trace *trace_dev = nullptr;
+    size_t trace_cap = 0, stage_bytes = 0;
+    unsigned char *stage = nullptr;  // pinned: [chains] records, [chains] states
+  } ms;
   // what the slots' buffers are carved from (one allocation per kind)
   double *slab_cellout = nullptr, *slab_reduced = nullptr, *slab_quad = nullptr, *slab_gpart = nullptr, *slab_reduced_host = nullptr;
   unsigned *slab_ticket = nullptr;
@@ -162,6 +177,7 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
                  bool on_aux_stream = false, bool relaunch_ok = false, bool allow_direct = true);
 int resident_quiesce(nid_ctx *ctx);  // ... and every ordinary evaluation launch (the resident workgroups hold most of every CU)
 void free_seq_pool(nid_ctx *ctx);
+void free_ms_pool(nid_ctx *ctx);
 
 #define NID_HIP(ctx, expr)                                                            \
   do {                                                                                \
@@ -312,6 +328,7 @@ int launch_eval2(nid_ctx *ctx, EvalParams &P, bool jac, hipStream_t stream, int 
   // still fit a CU (LDS 16 KB, 96 VGPRs).  Launches of few poses are latency bound: see pick_threads.
   const bool dbg = ctx->dbg_enabled || ctx->dbg_stamps != nullptr;
   int nt = pick_threads(ctx, jac, batch);
+  if (P.slots_ext && nt > 256) nt = 256;  // (records in device memory: the EXT kernels, whatever the batch -- nid_multistart_lm)
   // the diagnostic instantiations exist for 128 and 256 threads; phase stamps alone also for the latency form
   const bool stamps_lat = dbg && !ctx->dbg_enabled && !ctx->loop_form && ctx->math_mode != NID_MATH_STRICT && nt >= 512 &&
                           P.g.pstride <= lat_rounds(nt) * nt && batch <= kMaxBatch;
@@ -1393,6 +1410,7 @@ int nid_destroy(nid_ctx *ctx) {
   }
   if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
   free_seq_pool(ctx);
+  free_ms_pool(ctx);
   (void)hipFree(ctx->slab_cellout); (void)hipFree(ctx->slab_reduced); (void)hipFree(ctx->slab_quad);
   (void)hipFree(ctx->slab_ticket); (void)hipFree(ctx->slab_gpart);
   if (ctx->slab_reduced_host) (void)hipHostFree(ctx->slab_reduced_host);
@@ -2322,3 +2340,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // multi-GPU layer (include/nid/nid_multi.h): same translation unit, it drives the shard contexts' internals
 #include "nid_multi.inc"
+
+// ---- many LM chains at once, stepped on the device (include/nid/nid_multistart.h) ---
+#include "nid_multistart.inc"

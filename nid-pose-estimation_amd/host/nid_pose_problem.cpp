@@ -11,6 +11,8 @@
 
 #include "g2o_min/g2o_min.h"
 #include "nid/legacy_ops.h"
+#include "nid/nid_multi.h"
+#include "nid/nid_multistart.h"
 #include "nid_pose_problem.h"
 
 static double g_last_optimize_s = 0.0;
@@ -143,6 +145,47 @@ int nid_host_run_lm(const nid_pose_problem *pb, double *pose7_inout, nid_host_lm
   nid_legacy_quiesce();  // (a resident kernel leaves the device; the context stays for the next pair)
   stamp("trace copy, nid_legacy_quiesce");
   return done;
+}
+
+int nid_host_run_multistart_lm(const nid_pose_problem *pb, const double *poses7_in, int n, const double *pose_ref7,
+                               int max_rounds, nid_ms_result *results, int *best, nid_ms_trace *trace, int *rounds_done,
+                               char *log_buf, int log_cap) {
+  if (!pb || !poses7_in || !results || n < 1) return -1;
+  auto say = [&](const char *what, const char *detail) {
+    if (log_buf && log_cap > 0) std::snprintf(log_buf, (size_t)log_cap, "%s%s%s", what, detail[0] ? ": " : "", detail);
+  };
+  nid_legacy_set_jacobian_bound(pb->jac_bound_cuda ? 1 : 0);
+  nid_legacy_set_math_mode(pb->strict_math ? 1 : 0);
+  const int cell = pb->cell_num;
+  std::vector<double> intrinscis = {pb->fx, pb->fy, pb->cx, pb->cy, pb->depth_factor};
+  std::vector<double> Href(cell * cell, 0.0);
+  std::vector<int> bs_counter(cell * cell);
+  std::vector<double> T_wc0(pb->T_wc0_colmajor, pb->T_wc0_colmajor + 16);
+  g2o::Matrix4d M0 = g2o::SE3Quat::fromPose7(pose_ref7 ? pose_ref7 : poses7_in).to_homogeneous_matrix();
+  nid_multi *m = nid_legacy_set_pair_u16(pb->depth_u16, pb->im0, pb->im1, T_wc0.data(), M0.data(), intrinscis.data(), pb->bin_num, 3,
+                                         cell, pb->rows, pb->cols, bs_counter.data(), Href.data());
+  if (!m) {
+    say("the NID operators could not set up their device state (see stderr)", "");
+    nid_legacy_reset();
+    return -3;
+  }
+  int32_t rank = 0, world = 1;
+  (void)nid_multi_world(m, &rank, &world);
+  if (nid_multi_shards(m) != 1 || world != 1) {
+    say("nid_host_run_multistart_lm needs ONE device and rank: the chains are stepped on the device that evaluates them", "");
+    return -4;
+  }
+  nid_ctx *ctx = nid_multi_shard(m, 0);
+  const double delta = pb->huber_delta > 0 ? pb->huber_delta : std::sqrt(0.95);
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = nid_multistart_lm(ctx, poses7_in, n, pb->iterations, delta, max_rounds, results, best, trace, rounds_done);
+  g_last_optimize_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  if (rc != NID_OK) {
+    say(nid_status_string(rc), nid_last_error(ctx));
+    return -5;
+  }
+  if (log_buf && log_cap > 0) log_buf[0] = 0;
+  return 0;
 }
 
 void nid_host_se3_exp(const double *upd6, double *pose7) {

@@ -5,6 +5,8 @@
 #define NID_POSE_PROBLEM_H
 #include <stddef.h>
 #include <stdint.h>
+
+#include "nid/nid_multistart.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -39,6 +41,18 @@ typedef struct {
 /* returns the number of outer iterations done (or < 0); pose7 = {qx,qy,qz,qw,tx,ty,tz} in/out */
 int nid_host_run_lm(const nid_pose_problem *pb, double *pose7_inout, nid_host_lm_record *trace, int max_trace,
                     char *log_buf, int log_cap);
+
+/* Multi-start LM (include/nid/nid_multistart.h): n Levenberg-Marquardt chains from poses7_in (n x 7) on the pair of *pb,
+ * all of them advanced by one evaluation grid per round and stepped on the device; pb->iterations outer iterations at
+ * most, pb->fused is ignored.  The pair is set up the native way (nid_set_pair_u16 on the context the fused flows use:
+ * same Jacobian bound, math mode and launch shape) with the reference stage at pose_ref7 (NULL: the first start pose).
+ * results[n], *best, trace (may be NULL: max_rounds x n, or (1 + 10 iterations) x n for max_rounds = 0) and *rounds_done
+ * as nid_multistart_lm gives them.  Returns 0, or -1 bad arguments, -3 the device state could not be set up, -4 more than
+ * one device or rank is configured (nid_host_set_devices / nid_host_set_rank: the chains need one context that owns every
+ * cell), -5 nid_multistart_lm failed (its message in log_buf). */
+int nid_host_run_multistart_lm(const nid_pose_problem *pb, const double *poses7_in, int n, const double *pose_ref7,
+                               int max_rounds, nid_ms_result *results, int *best, nid_ms_trace *trace, int *rounds_done,
+                               char *log_buf, int log_cap);
 
 /* PNG input of the reference's driver (host/nid_png.cpp; zlib only).  Return 0, or -1 cannot open, -2 not a
  * PNG / corrupt, -3 unsupported variant, -4 inflate failed, -5 buffer too small.  With out == NULL only the

@@ -139,6 +139,38 @@ def run_lm(pair, bin_num, pose7, iterations=10, jac_bound_cuda=False, fused=Fals
     return p, recs, log.value.decode(errors="replace")
 
 
+def run_multistart_lm(pair, bin_num, poses7, iterations=10, pose_ref=None, max_rounds=0, trace=False, jac_bound_cuda=False,
+                      huber_delta=None, strict=False, synth=None):
+    """n LM chains from poses7 (n x 7) on one frame pair, stepped on the device (nid_host_run_multistart_lm); the reference
+    stage at pose_ref (default: the first start).  Returns (results, best, rounds_done[, trace]) as
+    capi.Context.multistart_lm does."""
+    import importlib
+    synth = synth or importlib.import_module("nid-pose-estimation_amd.synth")
+    capi = importlib.import_module("nid-pose-estimation_amd.capi")
+    pb, keep = _problem(pair, bin_num, iterations, jac_bound_cuda, 1, huber_delta, strict, synth)
+    lib = load()
+    lib.nid_host_run_multistart_lm.restype = C.c_int
+    lib.nid_host_run_multistart_lm.argtypes = [C.POINTER(PoseProblem), c_dp, C.c_int, c_dp, C.c_int, C.c_void_p, c_ip,
+                                               C.c_void_p, c_ip, C.c_char_p, C.c_int]
+    p = _d(np.asarray(poses7).reshape(-1, 7))
+    n = p.shape[0]
+    cap = int(max_rounds) if max_rounds > 0 else 1 + 10 * int(iterations)
+    res = np.zeros(max(n, 1), dtype=capi.MS_RESULT_DTYPE)
+    tr = np.zeros((cap, max(n, 1)), dtype=capi.MS_TRACE_DTYPE) if trace else None
+    ref = _d(pose_ref) if pose_ref is not None else None
+    best, rounds = C.c_int(-2), C.c_int(0)
+    log = C.create_string_buffer(4096)
+    rc = lib.nid_host_run_multistart_lm(C.byref(pb), _dp(p), n, _dp(ref) if ref is not None else None, int(max_rounds),
+                                        res.ctypes.data_as(C.c_void_p), C.byref(best),
+                                        tr.ctypes.data_as(C.c_void_p) if trace else None, C.byref(rounds), log, len(log))
+    del keep
+    if rc < 0:
+        raise RuntimeError(f"nid_host_run_multistart_lm failed ({rc}): " + log.value.decode(errors="replace"))
+    if trace:
+        return res[:n], int(best.value), int(rounds.value), tr[:rounds.value, :n]
+    return res[:n], int(best.value), int(rounds.value)
+
+
 def _problem(pair, bin_num, iterations, jac_bound_cuda, fused, huber_delta, strict, synth, legacy_setup=False):
     im0 = np.ascontiguousarray(pair.im0, dtype=np.uint8)
     im1 = np.ascontiguousarray(pair.im1, dtype=np.uint8)

@@ -1,0 +1,216 @@
+"""nid_lm_step_host alone: the per-chain Levenberg-Marquardt step of nid_multistart_lm (csrc/nid_lm_step.h, the function
+k_lm_step runs, compiled for the host), on reduced blocks made from synthetic quadratic costs.  No GPU."""
+import importlib
+
+import numpy as np
+import pytest
+
+EPS = np.finfo(np.float64).eps
+F_FIRST, F_ACCEPT, F_REJECT, F_OUTER_END, F_SOLVE_FAILED, F_FINISHED = 1, 2, 4, 8, 16, 32
+
+
+@pytest.fixture(scope="module")
+def hostlib():
+    return importlib.import_module("nid-pose-estimation_amd.hostlib")
+
+
+def block(H, b, chi2, na=16):
+    r = np.zeros(32)
+    r[0] = chi2
+    r[1:7] = b
+    r[7:28] = np.asarray(H)[np.triu_indices(6)]
+    r[28] = na
+    return r
+
+
+def spd(rng, scale=1.0, cond=1e3):
+    Q, _ = np.linalg.qr(rng.standard_normal((6, 6)))
+    return (Q * np.geomspace(1.0, cond, 6)) @ Q.T * scale
+
+
+POSE0 = np.array([0.01, -0.02, 0.03, 0.0, 0.4, -0.2, 1.5])
+POSE0[3] = np.sqrt(1.0 - (POSE0[:3] ** 2).sum())
+
+
+def fresh(capi, H, b, chi2=10.0, iterations=10, pose=POSE0):
+    st = capi.new_ms_state(pose, iterations)
+    assert capi.lm_step_host(st, block(H, b, chi2))
+    assert st.flags == F_FIRST and st.started == 1 and st.solve_ok == 1
+    return st
+
+
+def snapshot(st):
+    return bytes(memoryview(st))
+
+
+def system(st):
+    H = np.zeros((6, 6))
+    H[np.triu_indices(6)] = np.array(st.H)
+    H = H + np.triu(H, 1).T
+    return H + st.lambda_ * np.eye(6), np.array(st.b), np.array(st.x)
+
+
+def check_solve_and_trial(st, hostlib):
+    """properties 1, 2 and 4 of the state behind a step that solved"""
+    A, b, x = system(st)
+    res = np.abs(A @ x - b).max()
+    bound = 64 * EPS * (np.abs(A).sum(axis=1).max() * np.abs(x).max() + np.abs(b).max())
+    assert res <= bound, f"|(H + lambda I) x - b| = {res:.3e} > {bound:.3e}"
+    ref = hostlib.se3_mul(hostlib.se3_exp(x), np.array(st.pose7))
+    got = np.array(st.trial7)
+    assert np.abs(got[:4] - ref[:4]).max() <= 1e-13, f"quaternion off by {np.abs(got[:4] - ref[:4]).max():.3e}"
+    assert np.abs(got[4:] - ref[4:]).max() <= 1e-13 * max(1.0, np.abs(ref[4:]).max())
+    assert np.array(st.rec_q).tobytes() == got.tobytes() and st.rec_mode == st.xform_mode
+    M = hostlib.se3_to_matrix16(np.array(st.rec_q)).reshape(4, 4).T[:3]  # column-major 4x4 -> rows of [R|t]
+    assert np.abs(np.array(st.rec_M).reshape(3, 4) - M).max() <= 4 * EPS
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_solve_residual_trial_pose_and_record(capi, hostlib, seed):
+    """after every step of a chain on a quadratic cost: the damped system is solved to rounding, the trial pose is
+    exp(x) * current, the record's M is the rotation of its q"""
+    rng = np.random.default_rng(seed)
+    H = spd(rng, scale=10.0 ** rng.integers(-2, 3), cond=10.0 ** rng.integers(1, 5))
+    xs = rng.standard_normal(6) * 10.0 ** rng.uniform(-4, -1)  # the minimiser, in the tangent space of the current pose
+    cost = lambda d: 5.0 + 0.5 * (d - xs) @ H @ (d - xs)
+    st = fresh(capi, H, H @ xs, cost(np.zeros(6)))
+    check_solve_and_trial(st, hostlib)
+    for _ in range(12):
+        x = np.array(st.x)
+        before = np.array(st.pose7)
+        running = capi.lm_step_host(st, block(H, H @ (xs - x), cost(x)))
+        if st.flags & F_ACCEPT:  # the quadratic model moves with the pose: what is left of the minimiser
+            xs = xs - x
+            assert np.array(st.pose7).tobytes() != before.tobytes()
+        else:
+            assert np.array(st.pose7).tobytes() == before.tobytes()
+        if not running:
+            break
+        if st.solve_ok:
+            check_solve_and_trial(st, hostlib)
+    assert st.trials_total >= 1 and st.outer_done >= 1
+
+
+@pytest.mark.parametrize("theta", [0.0, 3e-6, 2e-5, 1e-3, 0.3, 0.9, 1.7, 3.0, 3.1415926, 4.5, 6.2, 40.0])
+def test_exponential_map_against_libm(capi, hostlib, theta):
+    """the written-out sin / cos (argument reduction in every quadrant) and the small-angle branch of the exponential map"""
+    axis = np.array([0.48, -0.6, 0.64])
+    u = np.concatenate([theta * axis, [0.3, -0.7, 0.2]])
+    st = fresh(capi, np.eye(6), u * (1 + 1e-5))  # H = I, lambda = 1e-5: x = u
+    assert np.abs(np.array(st.x) - u).max() <= 1e-14 * max(1.0, theta)
+    check_solve_and_trial(st, hostlib)
+
+
+def trial_with_rho(capi, rho, lam_before=None):
+    """a chain one step in, then a block whose chi2 gives the trial exactly the wanted gain ratio (to rounding)"""
+    rng = np.random.default_rng(7)
+    H = spd(rng)
+    b = rng.standard_normal(6) * 1e-2
+    st = fresh(capi, H, b, 10.0)
+    x = np.array(st.x)
+    scale = float(x @ (st.lambda_ * x + b)) + 1e-3
+    return st, H, b, 10.0 - rho * scale
+
+
+# 1 - (2 rho - 1)^3 crosses 2/3 at rho = 0.8467 and 1/3 at rho = 0.9368: both clamps from both sides, and far out
+@pytest.mark.parametrize("rho, factor", [(0.05, 2. / 3.), (0.5, 2. / 3.), (0.84, 2. / 3.), (0.85, None), (0.9, None), (0.93, None),
+                                         (0.94, 1. / 3.), (3.0, 1. / 3.)])
+def test_accept_and_the_lambda_clamps(capi, rho, factor):
+    st, H, b, chi2 = trial_with_rho(capi, rho)
+    lam, trial = st.lambda_, np.array(st.trial7)
+    H2, b2 = 2 * H, -b
+    assert capi.lm_step_host(st, block(H2, b2, chi2, na=9))
+    assert st.flags & (F_ACCEPT | F_OUTER_END) == (F_ACCEPT | F_OUTER_END) and not st.flags & F_REJECT
+    want = factor if factor is not None else 1.0 - (2 * rho - 1) ** 3
+    assert 1. / 3. < want < 2. / 3. or factor is not None
+    assert abs(st.lambda_ / lam - want) <= 1e-9, "lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3))"
+    assert abs(st.rho - rho) <= 1e-9 and st.ni == 2.0 and st.outer_done == 1 and st.trials == 0 and st.trials_total == 1
+    # the trial became the current pose with ITS block
+    assert np.array(st.pose7).tobytes() == trial.tobytes() and st.chi2 == chi2 and st.n_active == 9
+    assert np.array(st.b).tobytes() == b2.tobytes() and np.array(st.H).tobytes() == H2[np.triu_indices(6)].tobytes()
+
+
+def test_ten_rejections_exhaust_the_trials(capi):
+    st, H, b, _ = trial_with_rho(capi, 1.0)
+    pose, lam, ni = np.array(st.pose7), st.lambda_, 2.0
+    for k in range(10):
+        running = capi.lm_step_host(st, block(H, b, 11.0 + k))  # worse than the current 10.0: rho < 0
+        lam, ni = lam * ni, ni * 2
+        assert st.flags & F_REJECT and st.lambda_ == lam and st.ni == ni and st.rho < 0
+        assert running == (k < 9)
+        assert bool(st.flags & F_OUTER_END) == (k == 9)
+    assert st.status == capi.MS_TRIALS_EXHAUSTED and st.flags & F_FINISHED and st.trials_total == 10 and st.outer_done == 1
+    assert np.array(st.pose7).tobytes() == pose.tobytes() and st.chi2 == 10.0
+
+
+def test_rho_zero_ends_the_chain(capi):
+    st, H, b, chi2 = trial_with_rho(capi, 0.0)
+    assert chi2 == 10.0
+    assert not capi.lm_step_host(st, block(H, b, chi2))
+    assert st.rho == 0.0 and st.status == capi.MS_RHO_NOT_NEGATIVE and st.flags == F_REJECT | F_OUTER_END | F_FINISHED
+
+
+def test_nan_chi2_is_rejected_and_ends_the_outer_iteration(capi):
+    st, H, b, _ = trial_with_rho(capi, 1.0)
+    lam = st.lambda_
+    assert capi.lm_step_host(st, block(H, b, np.nan))
+    assert np.isnan(st.rho) and st.flags & (F_REJECT | F_OUTER_END) == (F_REJECT | F_OUTER_END)
+    assert st.status == capi.MS_RUNNING and st.outer_done == 1 and st.lambda_ == lam * 2 and st.ni == 4.0 and st.chi2 == 10.0
+    # (inf: rho = -inf, an ordinary rejection inside the outer iteration)
+    assert capi.lm_step_host(st, block(H, b, np.inf))
+    assert st.rho == -np.inf and st.flags & F_REJECT and not st.flags & F_OUTER_END and st.outer_done == 1
+
+
+def test_failed_solve_counts_as_dbl_max(capi):
+    """an indefinite H: the LDLT meets a negative pivot, x is kept, and the trial's evaluation counts as DBL_MAX whatever
+    its chi2 is; lambda grows until the damped system is positive"""
+    H = np.diag([4.0, 3.0, 2.0, 1.0, 1.0, -0.5])
+    b = np.array([1e-2, 0, 0, 0, 0, 1e-2])
+    st = capi.new_ms_state(POSE0, 10)
+    assert capi.lm_step_host(st, block(H, b, 10.0))
+    assert st.flags == F_FIRST | F_SOLVE_FAILED and st.solve_ok == 0 and not np.array(st.x).any()
+    assert np.abs(np.array(st.trial7) - np.array(st.pose7)).max() <= 2 * EPS, "exp(0) * pose (renormalised)"
+    lam = st.lambda_
+    assert lam == 1e-5 * 4.0
+    steps = 0
+    while not st.solve_ok:
+        assert capi.lm_step_host(st, block(H, b, 1.0))  # a BETTER chi2: ignored, the solve had failed
+        steps += 1
+        assert st.flags & F_REJECT and st.rho < -1e300 and st.chi2 == 10.0
+    assert st.lambda_ > 0.5 and steps == st.trials and 2 <= steps < 10
+    A, bb, x = system(st)
+    assert np.abs(A @ x - bb).max() <= 64 * EPS * (np.abs(A).sum(axis=1).max() * np.abs(x).max() + np.abs(bb).max())
+    # a singular but non-negative system is not a failure: zero pivots give zero components
+    st0 = capi.new_ms_state(POSE0, 10)
+    assert capi.lm_step_host(st0, block(np.zeros((6, 6)), np.zeros(6), 0.0, na=0))
+    assert st0.solve_ok == 1 and st0.lambda_ == 0.0 and not np.array(st0.x).any()
+    assert not capi.lm_step_host(st0, block(np.zeros((6, 6)), np.zeros(6), 0.0, na=0))
+    assert st0.rho == 0.0 and st0.status == capi.MS_RHO_NOT_NEGATIVE and st0.n_active == 0
+
+
+def test_three_flat_iterations_end_with_nbad_and_a_finished_chain_is_frozen(capi):
+    rng = np.random.default_rng(3)
+    H = spd(rng)
+    b = rng.standard_normal(6) * 1e-3
+    st = fresh(capi, H, b, 10.0)
+    chi2 = 10.0
+    for k in range(3):
+        chi2 -= 1e-6  # accepted (rho > 0), but less than a thousandth of the iteration's start
+        running = capi.lm_step_host(st, block(H, b, chi2))
+        assert st.flags & F_ACCEPT and st.n_bad == k + 1 and running == (k < 2)
+    assert st.status == capi.MS_NBAD and st.outer_done == 3
+    # a real gain in between resets the count
+    st2 = fresh(capi, H, b, 10.0)
+    for k, c in enumerate([10.0 - 1e-6, 9.0, 9.0 - 1e-6, 9.0 - 2e-6]):
+        assert capi.lm_step_host(st2, block(H, b, c))
+    assert st2.n_bad == 2 and st2.status == capi.MS_RUNNING
+    # `iterations` outer iterations
+    st3 = fresh(capi, H, b, 10.0, iterations=2)
+    assert capi.lm_step_host(st3, block(H, b, 9.0))
+    assert not capi.lm_step_host(st3, block(H, b, 8.0))
+    assert st3.status == capi.MS_ITERATIONS and st3.outer_done == 2
+    for fin in (st, st3):
+        snap = snapshot(fin)
+        for blk in (block(H, b, 1.0), block(2 * H, -b, np.nan), np.full(32, np.inf)):
+            assert not capi.lm_step_host(fin, blk)
+            assert snapshot(fin) == snap, "a finished chain changed"
