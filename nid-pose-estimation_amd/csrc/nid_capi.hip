@@ -23,6 +23,7 @@
 #include "nid/nid_c.h"
 #include "nid/nid_multistart.h"
 #include "nid_eval_launch.h"
+#include "nid_pose_pool.h"             // pose_sizes, seq_fusion: per-pose buffer sizes and the fused grids' budget rule (no HIP in it)
 #include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
 #include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
@@ -34,9 +35,6 @@ namespace {
 struct Slot {
   double *cellout_dev = nullptr;
   double *reduced_dev = nullptr;   // device scratch target (evaluate path / slot_buffers)
-  double *quad_dev = nullptr;      // per-cell quadratic forms
-  unsigned *ticket_dev = nullptr;  // [0] top, [1+g] groups
-  double *gpart_dev = nullptr;     // group sums
   double *cellout_host = nullptr;  // pinned, mapped: the blocking per-cell calls let the kernel write here directly
   double *cellout_host_devptr = nullptr;
   double *reduced_host = nullptr;  // pinned, mapped: [32 doubles][u64 sequence word]
@@ -60,6 +58,19 @@ struct Slot {
   bool external_target = false;
   int done_slot = 0;               // external targets: the slot whose `done` event covers this one's launch
 };
+
+// What every pose of a grid needs for itself: per-cell blocks, group sums, tickets (zero between launches: the kernels
+// leave them so) and -- for a private grid -- its argument record (pinned mirror + device array).  The public slots are
+// carved from one (no records); nid_run_sequence's fused grids and nid_multistart_lm each own one.  A private grid of
+// poses is run with pool_ensure, pool_record + the pose per record, and launch_records; pool_free with the context.
+struct PosePool {
+  size_t poses = 0;
+  double *quad = nullptr, *gpart = nullptr;          // [poses][nloc * kQuad], [poses][ngroups * kQuad]
+  unsigned *ticket = nullptr;                        // [poses][ticket words]
+  SlotArgs *rec_dev = nullptr, *rec_host = nullptr;  // [poses], or null
+};
+static_assert(sizeof(SlotArgs) == 224, "the budget rule's table (tests/cpp/pose_pool_check.cpp) assumes this record");
+static_assert(kPoseBlock == kQuad && kPoseBlock == kReducedLen && kSeqGridLimit == kSeqGridMax, "nid_pose_pool.h restates these");
 
 }  // namespace
 
@@ -142,31 +153,27 @@ struct nid_ctx {
   size_t seq_cap = 0;
   hipStream_t copy_stream = nullptr;
   // nid_run_sequence's FUSED grids (several consecutive batches of a long sequence in one grid of up to kSeqGridMax poses):
-  // what each pose of each grid in flight needs besides its result block in seq_dev / seq_host -- per-cell blocks, group
-  // sums, tickets (zero between launches, like the slots') and its argument record.  Private to the pipeline: the public
-  // slots are neither used nor marked pending by a fused sequence.  Made on first use (ensure_seq_pool), freed with the context.
+  // a PosePool of grid x depth poses, entry r of it beside the result blocks in seq_dev[r] / seq_host[r].  Private to the
+  // pipeline: the public slots are neither used nor marked pending by a fused sequence.  Made on first use (ensure_seq_pool).
   struct SeqPool {
     int grid = 0, depth = 0;  // poses per grid the pool is carved for, grids in flight
-    double *quad = nullptr, *gpart = nullptr;  // [depth][grid][nloc * kQuad], [depth][grid][ngroups * kQuad]
-    unsigned *ticket = nullptr;                // [depth][grid][ticket_words]
-    SlotArgs *rec_dev = nullptr, *rec_host = nullptr;  // [depth][grid]: a grid's records (pinned mirror, one in-stream copy)
+    PosePool poses;           // [depth][grid]
   } pool;
-  // nid_multistart_lm's buffers (nid_multistart.inc): per chain what a pose of a grid needs -- per-cell blocks, group sums,
-  // zeroed tickets, its record, its result block -- and the chain's state; per round one word (chains still running) and,
-  // when asked for, the trace.  Private to that call, grow only, freed with the context.
+  // nid_multistart_lm's buffers (nid_multistart.inc): a PosePool of `chains` poses, per chain its result block and its
+  // state; per round one word (chains still running) and, when asked for, the trace.  Private to that call, grow only.
   struct MsPool {
     int chains = 0, rounds = 0;
-    double *quad = nullptr, *gpart = nullptr, *reduced = nullptr;
-    unsigned *ticket = nullptr, *running_dev = nullptr, *running_host = nullptr;  // (running_host: pinned)
-    SlotArgs *rec_dev = nullptr;
-    nid_ms_state *state_dev = nullptr;
+    PosePool poses;
+    double *reduced = nullptr;
+    unsigned *running_dev = nullptr, *running_host = nullptr;  // (running_host: pinned)
+    nid_ms_state *state_dev = nullptr, *state_host = nullptr;  // (state_host: pinned, [chains])
     nid_ms_trace *trace_dev = nullptr;
-    size_t trace_cap = 0, stage_bytes = 0;
-    unsigned char *stage = nullptr;  // pinned: [chains] records, [chains] states
+    size_t trace_cap = 0;
   } ms;
-  // what the slots' buffers are carved from (one allocation per kind)
-  double *slab_cellout = nullptr, *slab_reduced = nullptr, *slab_quad = nullptr, *slab_gpart = nullptr, *slab_reduced_host = nullptr;
-  unsigned *slab_ticket = nullptr;
+  // what the slots' buffers are carved from (one allocation per kind; quad, gpart and tickets: slot_pool, without records)
+  PoseSizes sz{};  // per-pose sizes of this geometry (nid_pose_pool.h)
+  PosePool slot_pool;
+  double *slab_cellout = nullptr, *slab_reduced = nullptr, *slab_reduced_host = nullptr;
   std::string last_error;
 };
 
@@ -176,7 +183,6 @@ void resident_retire(nid_ctx *ctx);  // every call that changes what a resident 
 int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int want_jac, double delta, double *reduced_dev_base = nullptr,
                  bool on_aux_stream = false, bool relaunch_ok = false, bool allow_direct = true);
 int resident_quiesce(nid_ctx *ctx);  // ... and every ordinary evaluation launch (the resident workgroups hold most of every CU)
-void free_seq_pool(nid_ctx *ctx);
 void free_ms_pool(nid_ctx *ctx);
 
 #define NID_HIP(ctx, expr)                                                            \
@@ -370,7 +376,7 @@ void fill_common_params(nid_ctx *ctx, double delta, EvalParams *P) {
   P->huber_dsqr = (float)(delta * delta);  // RobustKernelHuber::setDelta, float dsqr (robust_kernel_impl.h:84)
   P->group_size = ctx->group_size;
   P->ctab = ctx->ctab_dev;
-  P->slots_ext = nullptr;  // launch_batch points it at a device array for more than kMaxBatch poses
+  P->slots_ext = nullptr;  // launch_records points it at a device array for more than kMaxBatch poses
   P->g = ctx->g;
   P->t = ctx->t;
   P->im1s = ctx->im1s_dev;
@@ -403,17 +409,77 @@ void fill_common_params(nid_ctx *ctx, double delta, EvalParams *P) {
   P->repair_queue = ctx->repair_queue_dev[0];  // (launch_eval2 picks the launch stream's)
 }
 
-void fill_slot_args(const Pose &pose, Slot &S, double *out_reduced, unsigned long long *host_seq, SlotArgs *A) {
-  A->pose = pose;
-  A->cellout = S.cellout_dev;
-  A->quad = S.quad_dev;
-  A->gpart = S.gpart_dev;
-  A->ticket = S.ticket_dev;
+// ---- per-pose buffers and records: PosePool ----------------------------------------------------------------------
+void pool_free(PosePool &Q) {
+  (void)hipFree(Q.quad); (void)hipFree(Q.gpart); (void)hipFree(Q.ticket); (void)hipFree(Q.rec_dev);
+  if (Q.rec_host) (void)hipHostFree(Q.rec_host);
+  Q = PosePool();
+}
+
+// the pool for exactly `poses` poses (a context's geometry is fixed: only their number changes between calls)
+int pool_ensure(nid_ctx *ctx, PosePool &Q, size_t poses, bool with_records) {
+  if (Q.poses == poses) return NID_OK;
+  resident_retire(ctx);  // (hipFree waits for the whole device)
+  pool_free(Q);
+  int rc;
+  if ((rc = dev_alloc(ctx, &Q.quad, poses * ctx->sz.quad))) return rc;
+  if ((rc = dev_alloc(ctx, &Q.gpart, poses * ctx->sz.gpart))) return rc;
+  if ((rc = dev_alloc(ctx, &Q.ticket, poses * ctx->sz.ticket))) return rc;
+  NID_HIP(ctx, hipMemset(Q.ticket, 0, poses * ctx->sz.ticket * sizeof(unsigned)));  // (the kernels leave them zero behind every launch)
+  if (with_records) {
+    if ((rc = dev_alloc(ctx, &Q.rec_dev, poses))) return rc;
+    if (hipHostMalloc(reinterpret_cast<void **>(&Q.rec_host), poses * sizeof(SlotArgs), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
+  }
+  Q.poses = poses;
+  return NID_OK;
+}
+
+// everything of pool pose i's record except the pose: its buffers, where its result block goes, and the defaults of a
+// launch nobody watches from the host (no per-cell outputs, no sequence word, in-launch reduction)
+void pool_record(const nid_ctx *ctx, const PosePool &Q, size_t i, double *out_reduced, SlotArgs *A) {
+  A->cellout = nullptr;
+  A->quad = Q.quad + i * ctx->sz.quad;
+  A->gpart = Q.gpart + i * ctx->sz.gpart;
+  A->ticket = Q.ticket + i * ctx->sz.ticket;
   A->out_reduced = out_reduced;
-  A->host_seq = host_seq;
-  A->launch_seq = S.seq;
+  A->host_seq = nullptr;
+  A->launch_seq = 0;
   A->cellout_host = 0;
   A->host_quad = 0;
+}
+
+// a public slot's record: its part of slot_pool, its per-cell outputs and its sequence number
+void fill_slot_args(const nid_ctx *ctx, const Pose &pose, const Slot &S, double *out_reduced, unsigned long long *host_seq, SlotArgs *A) {
+  pool_record(ctx, ctx->slot_pool, (size_t)(&S - ctx->slots), out_reduced, A);
+  A->pose = pose;
+  A->cellout = S.cellout_dev;
+  A->host_seq = host_seq;
+  A->launch_seq = S.seq;
+}
+
+// ONE grid from n filled records (P: fill_common_params).  Up to kMaxBatch poses the records ride in the kernel
+// arguments (recs may be P.slot itself: filled in place); beyond, or with `on_device` (nid_multistart_lm: k_lm_step
+// rewrites the poses there), one in-stream copy takes them to recs_dev and the kernel reads them from it -- recs == null:
+// they are there already.  e0 / e1: timing events right in front of and behind k_eval2 (e1 in front of k_repair).
+int launch_records(nid_ctx *ctx, EvalParams &P, const SlotArgs *recs, int n, SlotArgs *recs_dev, bool on_device, bool jac, hipStream_t st,
+                   hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+  if (n <= kMaxBatch && !on_device) {
+    if (recs != P.slot) std::copy(recs, recs + n, P.slot);
+  } else {
+    if (recs) NID_HIP(ctx, hipMemcpyAsync(recs_dev, recs, (size_t)n * sizeof(SlotArgs), hipMemcpyHostToDevice, st));
+    P.slots_ext = recs_dev;
+  }
+  if (e0) NID_HIP(ctx, hipEventRecord(e0, st));
+  return launch_eval2(ctx, P, jac, st, n, e1);
+}
+
+bool any_pending(const nid_ctx *ctx, int first = 0, int n = NID_SLOTS) {
+  return std::any_of(ctx->slots + first, ctx->slots + first + n, [](const Slot &S) { return S.pending; });
+}
+// a slot's result has not been collected: a second launch would silently replace it
+int refuse_pending(nid_ctx *ctx) {
+  ctx->last_error = "slot still pending: nid_wait() it first";
+  return NID_ERR_STATE;
 }
 
 // ---- DIRECT launches ---------------------------------------------------------------------------------------------
@@ -740,7 +806,7 @@ int wait_direct_cellout(nid_ctx *ctx, Slot &S) {
 void fill_eval_params(nid_ctx *ctx, const Pose &pose, Slot &S, double delta, double *out_reduced,
                       unsigned long long *host_seq, EvalParams *P) {
   fill_common_params(ctx, delta, P);
-  fill_slot_args(pose, S, out_reduced, host_seq, &P->slot[0]);
+  fill_slot_args(ctx, pose, S, out_reduced, host_seq, &P->slot[0]);
 }
 
 int check_ready(nid_ctx *ctx) {
@@ -762,16 +828,16 @@ int timing_events(nid_ctx *ctx, Slot &S) {
 // ---- the RESIDENT evaluator (k_resident): host side -- nid_capi_resident.inc, this translation unit ---
 #include "nid_capi_resident.inc"
 
+// one pose into one slot.  on_aux_stream: the awaited cost-only pose of nid_launch_chain, which runs beside the chain's
+// Jacobian launch -- an ordinary launch with DIRECT records on the context's second stream, never the resident kernel
+// (it serves ctx->stream's requests) and never GROUP-DIRECT
 int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double delta,
-                void *reduced_target) {
+                void *reduced_target, bool on_aux_stream = false) {
   int rc = check_ready(ctx);
   if (rc) return rc;
   if (slot < 0 || slot >= NID_SLOTS) return NID_ERR_INVALID_ARG;
   Slot &S = ctx->slots[slot];
-  if (S.pending) {  // its result has not been collected: a second launch would silently replace it
-    ctx->last_error = "slot still pending: nid_wait() it first";
-    return NID_ERR_STATE;
-  }
+  if (S.pending) return refuse_pending(ctx);
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   S.seq++;
   S.external_target = reduced_target != nullptr;
@@ -785,14 +851,15 @@ int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double d
     S.direct = true;
     S.direct_jac = want_jac != 0;
     S.direct_delta = delta;
-    if (ctx->direct_mode != 2 && resident_usable(ctx) && resident_post(ctx, slot, pose, want_jac != 0, false) == NID_OK) {
+    const bool groups = ctx->direct_mode == 2 && !on_aux_stream;
+    if (!groups && !on_aux_stream && resident_usable(ctx) && resident_post(ctx, slot, pose, want_jac != 0, false) == NID_OK) {
       S.resident = true;  // no launch at all: the resident kernel has the request
       S.timed = false;
       S.done_slot = slot;
       S.pending = true;
       return NID_OK;
     }
-    if (ctx->direct_mode == 2) {  // GROUP-DIRECT: the in-launch tail up to the group sums, those straight to the host
+    if (groups) {  // GROUP-DIRECT: the in-launch tail up to the group sums, those straight to the host
       rc = ensure_groups_host(ctx, S);
       if (rc) return rc;
       P.slot[0].out_reduced = S.groups_host_devptr;
@@ -819,7 +886,7 @@ int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double d
   }
   // single-pose launches stay on one in-order stream (alternating streams per single-pose launch measured
   // 2.2x slower); the batched pipeline of nid_run_sequence is the one that alternates
-  hipStream_t st = ctx->stream;
+  hipStream_t st = (on_aux_stream && !ctx->external_stream) ? ctx->aux_stream : ctx->stream;
   S.timed = ctx->timing;
   if (S.timed) { rc = timing_events(ctx, S); if (rc) return rc; }
   if (S.timed) NID_HIP(ctx, hipEventRecord(S.e0, st));
@@ -840,12 +907,11 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   if (rc) return rc;
   if (n < 1 || n > kMaxBatchExt || first_slot < 0 || first_slot + n > NID_SLOTS) return NID_ERR_INVALID_ARG;
   if (ctx->dbg_enabled) return NID_ERR_STATE;  // the per-pixel dump describes one pose
-  if (!relaunch_ok)  // (nid_time_launches re-issues the same launch on one in-order stream on purpose)
-    for (int k = 0; k < n; k++)
-      if (ctx->slots[first_slot + k].pending) {
-        ctx->last_error = "slot still pending: nid_wait() it first";
-        return NID_ERR_STATE;
-      }
+  // (nid_time_launches re-issues the same launch on one in-order stream on purpose)
+  if (!relaunch_ok && any_pending(ctx, first_slot, n)) return refuse_pending(ctx);
+  // one pose whose result the host waits for: the form nid_launch takes (DIRECT, GROUP-DIRECT or the resident kernel)
+  if (n == 1 && !reduced_dev_base && !relaunch_ok && allow_direct && direct_ok(ctx))
+    return launch_slot(ctx, first_slot, poses[0], want_jac, delta, nullptr, on_aux_stream);
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   EvalParams P{};
   fill_common_params(ctx, delta, &P);
@@ -861,53 +927,25 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
       ctx->ext_busy[ring] = false;
     }
     recs = ctx->ext_host[ring];
-    P.slots_ext = ctx->ext_dev[ring];
   }
-  // (one awaited pose in GROUP-DIRECT mode, nid_set_direct_results(ctx, 2): the same form nid_launch takes)
-  if (n == 1 && !reduced_dev_base && !relaunch_ok && allow_direct && !on_aux_stream && ctx->direct_mode == 2 && direct_ok(ctx))
-    return launch_slot(ctx, first_slot, poses[0], want_jac, delta, nullptr);
-  const bool direct = n == 1 && !reduced_dev_base && !relaunch_ok && allow_direct && direct_ok(ctx);
-  if (direct && !on_aux_stream && resident_usable(ctx) && resident_post(ctx, first_slot, poses[0], want_jac != 0, false) == NID_OK) {
-    Slot &S = ctx->slots[first_slot];
-    S.seq++;
-    S.external_target = false;
-    S.direct = S.resident = true;
-    S.direct_jac = want_jac != 0;
-    S.direct_delta = delta;
-    S.timed = false;
-    S.done_slot = first_slot;
-    S.pending = true;
-    return NID_OK;
-  }
-  if (direct) { rc = ensure_quad_host(ctx, ctx->slots[first_slot]); if (rc) return rc; }
   for (int k = 0; k < n; k++) {
     Slot &S = ctx->slots[first_slot + k];
     S.seq++;
     S.direct = S.resident = false;
     S.external_target = reduced_dev_base != nullptr;
     if (S.external_target) {  // caller-owned device buffer: pose k's block at base + k*32 (the pipelined loops, multi-GPU all-reduce)
-      fill_slot_args(poses[k], S, reduced_dev_base + (size_t)k * kReducedLen, nullptr, &recs[k]);
+      fill_slot_args(ctx, poses[k], S, reduced_dev_base + (size_t)k * kReducedLen, nullptr, &recs[k]);
       if (n > kMaxBatch) recs[k].cellout = nullptr;  // nobody reads the per-cell outputs of such a launch
     }
     else
-      fill_slot_args(poses[k], S, S.reduced_host_devptr,
+      fill_slot_args(ctx, poses[k], S, S.reduced_host_devptr,
                      reinterpret_cast<unsigned long long *>(S.reduced_host_devptr + kReducedLen), &recs[k]);
-    if (direct) {
-      recs[k].quad = S.quad_host_devptr;
-      recs[k].host_quad = 1;
-      S.quad_dirty = true;
-      S.direct = true;
-      S.direct_jac = want_jac != 0;
-      S.direct_delta = delta;
-    }
   }
-  if (ring >= 0)
-    NID_HIP(ctx, hipMemcpyAsync(ctx->ext_dev[ring], recs, (size_t)n * sizeof(SlotArgs), hipMemcpyHostToDevice, st));
   Slot &S0 = ctx->slots[first_slot];
   S0.timed = ctx->timing;
   if (S0.timed) { rc = timing_events(ctx, S0); if (rc) return rc; }
-  if (S0.timed) NID_HIP(ctx, hipEventRecord(S0.e0, st));
-  rc = launch_eval2(ctx, P, want_jac != 0, st, n, S0.timed ? S0.e1 : nullptr);  // (timed: e1 right behind k_eval2, in front of k_repair)
+  // (timed: e0 behind the record copy, e1 right behind k_eval2, in front of k_repair)
+  rc = launch_records(ctx, P, recs, n, ring >= 0 ? ctx->ext_dev[ring] : nullptr, false, want_jac != 0, st, S0.timed ? S0.e0 : nullptr, S0.timed ? S0.e1 : nullptr);
   if (rc) return rc;
   if (ring >= 0) {
     NID_HIP(ctx, hipEventRecord(ctx->ext_done[ring], st));
@@ -956,8 +994,7 @@ int launch_split(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   if (n < 1 || n > kMaxBatchExt || first_slot < 0 || first_slot + n > NID_SLOTS) return NID_ERR_INVALID_ARG;
   const SplitPlan plan = plan_split(ctx, n, want_jac != 0);
   if (plan.chunk >= n || ctx->dbg_enabled || ctx->timing) return launch_batch(ctx, first_slot, n, poses, want_jac, delta);
-  for (int k = 0; k < n; k++)  // all or nothing: no half-launched sequence
-    if (ctx->slots[first_slot + k].pending) { ctx->last_error = "slot still pending: nid_wait() it first"; return NID_ERR_STATE; }
+  if (any_pending(ctx, first_slot, n)) return refuse_pending(ctx);  // all or nothing: no half-launched sequence
   int l = 0;
   for (int i = 0; i < n; i += plan.chunk, l++) {
     const int cnt = std::min(plan.chunk, n - i);
@@ -1299,6 +1336,7 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   // two-level reduction geometry: ~sqrt(nloc) cells per group
   ctx->group_size = std::max(1, (int)std::ceil(std::sqrt((double)g.nloc)));
   ctx->ngroups = (g.nloc + ctx->group_size - 1) / ctx->group_size;
+  ctx->sz = pose_sizes(g.nloc, ctx->ngroups);
   int rc;
   if ((rc = dev_alloc(ctx, &ctx->t.X, plane))) return fail(rc);
   if ((rc = dev_alloc(ctx, &ctx->t.Y, plane))) return fail(rc);
@@ -1339,15 +1377,11 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   {
     // Per-slot buffers come out of ONE allocation per kind (NID_SLOTS x 5 hipMalloc + 2 hipHostMalloc calls used to be
     // most of the context's creation time); the slots hold pointers into the slabs.
-    const size_t n_cellout = (size_t)g.nloc * kCellOut, n_quad = (size_t)g.nloc * kQuad;
-    const size_t n_ticket = ((size_t)ctx->ngroups + 4 + 3) & ~(size_t)3, n_gpart = (size_t)ctx->ngroups * kQuad;
+    const size_t n_cellout = (size_t)g.nloc * kCellOut;
     const size_t n_rhost = kReducedLen + 2;  // [32 doubles][u64 sequence word][pad]
     if ((rc = dev_alloc(ctx, &ctx->slab_cellout, n_cellout * NID_SLOTS))) return fail(rc);
     if ((rc = dev_alloc(ctx, &ctx->slab_reduced, (size_t)kReducedLen * NID_SLOTS))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->slab_quad, n_quad * NID_SLOTS))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->slab_ticket, n_ticket * NID_SLOTS))) return fail(rc);
-    if (hipMemset(ctx->slab_ticket, 0, n_ticket * NID_SLOTS * sizeof(unsigned)) != hipSuccess) return fail(NID_ERR_HIP);
-    if ((rc = dev_alloc(ctx, &ctx->slab_gpart, n_gpart * NID_SLOTS))) return fail(rc);
+    if ((rc = pool_ensure(ctx, ctx->slot_pool, NID_SLOTS, false))) return fail(rc);  // pose s of it is slot s's (fill_slot_args)
     if (hipHostMalloc(reinterpret_cast<void **>(&ctx->slab_reduced_host), n_rhost * NID_SLOTS * sizeof(double),
                       hipHostMallocMapped) != hipSuccess) return fail(NID_ERR_NOMEM);
     std::memset(ctx->slab_reduced_host, 0, n_rhost * NID_SLOTS * sizeof(double));
@@ -1357,9 +1391,6 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
       Slot &S = ctx->slots[s];
       S.cellout_dev = ctx->slab_cellout + n_cellout * s;
       S.reduced_dev = ctx->slab_reduced + (size_t)kReducedLen * s;
-      S.quad_dev = ctx->slab_quad + n_quad * s;
-      S.ticket_dev = ctx->slab_ticket + n_ticket * s;
-      S.gpart_dev = ctx->slab_gpart + n_gpart * s;
       S.reduced_host = ctx->slab_reduced_host + n_rhost * s;
       S.reduced_host_devptr = rhost_dev + n_rhost * s;
       if (hipEventCreateWithFlags(&S.done, hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
@@ -1409,10 +1440,10 @@ int nid_destroy(nid_ctx *ctx) {
     if (ctx->seq_fence[r]) (void)hipEventDestroy(ctx->seq_fence[r]);
   }
   if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-  free_seq_pool(ctx);
+  pool_free(ctx->pool.poses);
   free_ms_pool(ctx);
-  (void)hipFree(ctx->slab_cellout); (void)hipFree(ctx->slab_reduced); (void)hipFree(ctx->slab_quad);
-  (void)hipFree(ctx->slab_ticket); (void)hipFree(ctx->slab_gpart);
+  pool_free(ctx->slot_pool);
+  (void)hipFree(ctx->slab_cellout); (void)hipFree(ctx->slab_reduced);
   if (ctx->slab_reduced_host) (void)hipHostFree(ctx->slab_reduced_host);
   for (int s = 0; s < NID_SLOTS; s++) {
     Slot &S = ctx->slots[s];
@@ -1476,8 +1507,7 @@ int nid_set_stream(nid_ctx *ctx, void *hip_stream) {
   // queue 0 without being ordered -- k_repair of the one could read or reset the count while k_eval2 of the other
   // pushes, and a lost cell never publishes (its nid_wait would run into the time-out).  So: no switch while a launch
   // is uncollected, and the old streams are drained (k_repair behind a collected launch may still be running).
-  for (int s = 0; s < NID_SLOTS; s++)
-    if (ctx->slots[s].pending) { ctx->last_error = "nid_set_stream: a launch is still pending: nid_wait() it first"; return NID_ERR_STATE; }
+  if (any_pending(ctx)) { ctx->last_error = "nid_set_stream: a launch is still pending: nid_wait() it first"; return NID_ERR_STATE; }
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   resident_retire(ctx);
   if (ctx->stream) NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1817,8 +1847,7 @@ int nid_set_short_sequence_policy(nid_ctx *ctx, int poses_per_launch, int stream
 int nid_launch_chain(nid_ctx *ctx, int first_slot, int n, const double *poses7, int n_jac, double delta) {
   if (!ctx || !poses7 || n < 1 || n > kMaxBatchExt || n_jac < 0 || n_jac > n) return NID_ERR_INVALID_ARG;
   if (first_slot < 0 || first_slot + n > NID_SLOTS) return NID_ERR_INVALID_ARG;
-  for (int k = 0; k < n; k++)  // all or nothing: no half-launched chain
-    if (ctx->slots[first_slot + k].pending) { ctx->last_error = "slot still pending: nid_wait() it first"; return NID_ERR_STATE; }
+  if (any_pending(ctx, first_slot, n)) return refuse_pending(ctx);  // all or nothing: no half-launched chain
   Pose p[kMaxBatchExt];
   for (int k = 0; k < n; k++) pose_from_pose7(poses7 + 7 * k, ctx->xform, &p[k]);
   int rc = NID_OK;
@@ -1865,57 +1894,14 @@ int ensure_seq_ring(nid_ctx *ctx, int batch) {
 // batches in one grid, F as large as kSeqGridMax allows.  Such a grid is beyond what the public slots can hold in flight
 // (NID_SLOTS / kSeqGridMax = one), so its poses' buffers come out of a pool of the pipeline's own.
 //
-// kSeqPoolBudget caps the pool's device memory.  Per pose: quad nloc x 32 doubles, gpart ngroups x 32 doubles, tickets,
-// a result block and a record (~0.5 KB together).
-//   config A (640x480, 256 cells, 16 groups): 64 KB + 4 KB + 0.5 KB = 68.5 KB; a 1024-pose grid 68.5 MB; 4 in flight 274 MB
-//   config B (1280x960, 1024 cells, 32 groups): 256 KB + 8 KB + 0.6 KB = 264.6 KB; a 1024-pose grid 264.6 MB; 4 in flight
-//     1058 MB is over, 3 in flight 794 MB
-// (the public slots of config B hold 1024 x (256 KB quad + 80 KB cellout + 8 KB gpart) = 344 MB).  Over budget at two
-// grids in flight, F goes down instead -- to 1, the unfused pipeline, at worst.
-constexpr size_t kSeqPoolBudget = (size_t)1 << 30;
-constexpr int kSeqPoolMinDepth = 2, kSeqPoolMaxDepth = 4;  // grids in flight (two streams: at least one each)
+// The budget rule -- how many batches per grid, how many grids in flight -- is seq_fusion of nid_pose_pool.h.
 
-size_t seq_ticket_words(const nid_ctx *ctx) { return ((size_t)ctx->ngroups + 4 + 3) & ~(size_t)3; }  // (a slot's: nid_create)
-
-size_t seq_pool_bytes_per_pose(const nid_ctx *ctx) {
-  return ((size_t)ctx->g.nloc + (size_t)ctx->ngroups + 1) * kQuad * sizeof(double) + seq_ticket_words(ctx) * sizeof(unsigned) + sizeof(SlotArgs);
-}
-
-// batches per grid of a long sequence (1: not fused) and how many such grids are in flight
-int seq_fusion(const nid_ctx *ctx, int batch, int *depth) {
-  int F = std::max(1, kSeqGridMax / batch);
-  const size_t per_pose = seq_pool_bytes_per_pose(ctx);
-  while (F > 1 && (size_t)kSeqPoolMinDepth * F * batch * per_pose > kSeqPoolBudget) F--;
-  *depth = (int)std::min<size_t>(kSeqPoolMaxDepth, std::max<size_t>(kSeqPoolMinDepth, kSeqPoolBudget / ((size_t)F * batch * per_pose)));
-  return F;
-}
-
-void free_seq_pool(nid_ctx *ctx) {
-  nid_ctx::SeqPool &Q = ctx->pool;
-  (void)hipFree(Q.quad); (void)hipFree(Q.gpart); (void)hipFree(Q.ticket); (void)hipFree(Q.rec_dev);
-  if (Q.rec_host) (void)hipHostFree(Q.rec_host);
-  Q = nid_ctx::SeqPool();
-}
-
-// the pool for `depth` grids of `grid` poses in flight (a context's geometry is fixed: what changes between calls is the
-// batch, and with it the grid); the result blocks are the ring's (ensure_seq_ring)
+// the pool for `depth` grids of `grid` poses in flight; the result blocks are the ring's (ensure_seq_ring)
 int ensure_seq_pool(nid_ctx *ctx, int grid, int depth) {
-  nid_ctx::SeqPool &Q = ctx->pool;
-  { int rc = ensure_seq_ring(ctx, grid); if (rc) return rc; }
-  if (Q.grid == grid && Q.depth == depth) return NID_OK;
-  resident_retire(ctx);  // (hipFree waits for the whole device)
-  free_seq_pool(ctx);
-  const size_t poses = (size_t)grid * depth, n_ticket = seq_ticket_words(ctx);
-  int rc;
-  if ((rc = dev_alloc(ctx, &Q.quad, poses * ctx->g.nloc * kQuad))) return rc;
-  if ((rc = dev_alloc(ctx, &Q.gpart, poses * ctx->ngroups * kQuad))) return rc;
-  if ((rc = dev_alloc(ctx, &Q.ticket, poses * n_ticket))) return rc;
-  NID_HIP(ctx, hipMemset(Q.ticket, 0, poses * n_ticket * sizeof(unsigned)));  // (the kernels leave them zero behind every launch)
-  if ((rc = dev_alloc(ctx, &Q.rec_dev, poses))) return rc;
-  if (hipHostMalloc(reinterpret_cast<void **>(&Q.rec_host), poses * sizeof(SlotArgs), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
-  Q.grid = grid;
-  Q.depth = depth;
-  return NID_OK;
+  int rc = ensure_seq_ring(ctx, grid);
+  if (rc == NID_OK) rc = pool_ensure(ctx, ctx->pool.poses, (size_t)grid * depth, true);
+  if (rc == NID_OK) { ctx->pool.grid = grid; ctx->pool.depth = depth; }
+  return rc;
 }
 
 // one grid of the fused pipeline: n <= pool.grid poses with pool entry r's buffers, results to seq_dev[r]; one record
@@ -1927,27 +1913,15 @@ int launch_seq_grid(nid_ctx *ctx, int r, int n, const double *poses7, int want_j
   if (n < 1 || n > Q.grid || r < 0 || r >= Q.depth) return NID_ERR_INVALID_ARG;
   EvalParams P{};
   fill_common_params(ctx, delta, &P);
-  const size_t base = (size_t)r * Q.grid, n_quad = (size_t)ctx->g.nloc * kQuad, n_gpart = (size_t)ctx->ngroups * kQuad, n_ticket = seq_ticket_words(ctx);
-  // (the ragged end of a sequence may be <= kMaxBatch poses: records in the kernel arguments, like every such launch)
-  SlotArgs *recs = n > kMaxBatch ? Q.rec_host + base : P.slot;
+  const size_t base = (size_t)r * Q.grid;
+  // (the ragged end of a sequence may be <= kMaxBatch poses: records in the kernel arguments, like every such launch;
+  // the result is on the device: the copy behind the launch and its event say when it is home)
+  SlotArgs *recs = n > kMaxBatch ? Q.poses.rec_host + base : P.slot;
   for (int k = 0; k < n; k++) {
-    SlotArgs &A = recs[k];
-    pose_from_pose7(poses7 + 7 * (size_t)k, ctx->xform, &A.pose);
-    A.cellout = nullptr;  // nobody reads the per-cell outputs of such a launch
-    A.quad = Q.quad + (base + k) * n_quad;
-    A.gpart = Q.gpart + (base + k) * n_gpart;
-    A.ticket = Q.ticket + (base + k) * n_ticket;
-    A.out_reduced = ctx->seq_dev[r] + (size_t)k * kReducedLen;
-    A.host_seq = nullptr;  // (the result is on the device: the copy behind the launch and its event say when it is home)
-    A.launch_seq = 0;
-    A.cellout_host = 0;
-    A.host_quad = 0;
+    pool_record(ctx, Q.poses, base + k, ctx->seq_dev[r] + (size_t)k * kReducedLen, &recs[k]);
+    pose_from_pose7(poses7 + 7 * (size_t)k, ctx->xform, &recs[k].pose);
   }
-  if (n > kMaxBatch) {
-    P.slots_ext = Q.rec_dev + base;
-    NID_HIP(ctx, hipMemcpyAsync(Q.rec_dev + base, recs, (size_t)n * sizeof(SlotArgs), hipMemcpyHostToDevice, st));
-  }
-  return launch_eval2(ctx, P, want_jac != 0, st, n);
+  return launch_records(ctx, P, recs, n, Q.poses.rec_dev + base, false, want_jac != 0, st);
 }
 }  // namespace
 
@@ -1968,7 +1942,7 @@ int nid_run_sequence(nid_ctx *ctx, const double *poses7, int n, int batch, int w
   // the unit all of this is counted in; a pose's bits do not depend on the grid it went in.
   if (!ctx || !poses7 || n < 0 || batch < 1 || batch > kMaxBatchExt) return NID_ERR_INVALID_ARG;
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-  for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
+  if (any_pending(ctx)) return NID_ERR_STATE;
   if (n <= batch) {
     // Nothing to pipeline, latency is what counts -- the kernel writes every pose's block straight to pinned host
     // memory and the host spins on the sequence words (no copy, no event: 128 us instead of 193 us from the enqueue
@@ -1987,7 +1961,7 @@ int nid_run_sequence(nid_ctx *ctx, const double *poses7, int n, int batch, int w
   }
   // (timed and diagnostic launches are per slot: such contexts keep the unfused form)
   int pool_depth = 0;
-  const int F = (ctx->timing || ctx->dbg_enabled || ctx->dbg_stamps) ? 1 : seq_fusion(ctx, batch, &pool_depth);
+  const int F = (ctx->timing || ctx->dbg_enabled || ctx->dbg_stamps) ? 1 : seq_fusion(ctx->g.nloc, ctx->ngroups, sizeof(SlotArgs), batch, &pool_depth);
   const bool fused = F > 1 && (long)n >= 2L * F * batch;
   const int unit = fused ? F * batch : batch;  // poses per grid
   const int depth = fused ? pool_depth : std::min((int)nid_ctx::kSeqRing, NID_SLOTS / batch);
@@ -2190,7 +2164,7 @@ int nid_set_href_nan_markers(nid_ctx *ctx, int on) {
 
 int nid_set_direct_results(nid_ctx *ctx, int on) {
   if (!ctx) return NID_ERR_INVALID_ARG;
-  for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
+  if (any_pending(ctx)) return NID_ERR_STATE;
   if (on < 0 || on > 2) return NID_ERR_INVALID_ARG;
   ctx->direct_results = on != 0;
   ctx->direct_mode = on;
@@ -2199,7 +2173,7 @@ int nid_set_direct_results(nid_ctx *ctx, int on) {
 
 int nid_set_resident(nid_ctx *ctx, int on) {
   if (!ctx) return NID_ERR_INVALID_ARG;
-  for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
+  if (any_pending(ctx)) return NID_ERR_STATE;
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   if (!on) {
     resident_retire(ctx);
@@ -2217,7 +2191,7 @@ int nid_set_resident(nid_ctx *ctx, int on) {
 int nid_resident_pause(nid_ctx *ctx) {
   if (!ctx) return NID_ERR_INVALID_ARG;
   if (!ctx->res.running) return NID_OK;
-  for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
+  if (any_pending(ctx)) return NID_ERR_STATE;
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   resident_retire(ctx);  // (the next request starts another)
   return NID_OK;
@@ -2254,29 +2228,36 @@ int nid_last_kernel_ms(nid_ctx *ctx, int slot, float *eval_ms, float *reduce_ms)
   return NID_OK;
 }
 
+// nid_time_launches / nid_time_kernel: argument check, the poses, and where the launches' result blocks go -- launches of
+// more than kMaxBatch poses are what the pipelined loop issues: they write them to a device buffer like there
+// (nid_run_sequence); smaller ones to pinned host memory like the blocking calls (null)
+static int time_prepare(nid_ctx *ctx, int n, const double *poses7, const float *out, int repeats, Pose *p, double **target) {
+  if (!ctx || !poses7 || !out || n < 1 || n > kMaxBatchExt || repeats < 1) return NID_ERR_INVALID_ARG;
+  NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
+  if (any_pending(ctx)) return NID_ERR_STATE;
+  for (int k = 0; k < n; k++) pose_from_pose7(poses7 + 7 * k, ctx->xform, &p[k]);
+  *target = nullptr;
+  if (n > kMaxBatch) {
+    int rc = ensure_seq_ring(ctx, n);
+    if (rc) return rc;
+    *target = ctx->seq_dev[0];
+  }
+  return NID_OK;
+}
+
 int nid_time_launches(nid_ctx *ctx, int n, const double *poses7, int want_jac, double delta, int repeats,
                       float *ms_per_launch) {
   // `repeats` identical n-pose launches back to back on the context's stream between two events: the
   // per-launch duration a kernel trace reports (event pairs around ONE launch add ~5 us of marker and
   // dispatch latency to a ~50 us kernel).  Same-stream launches are serialised, so reusing the slots is safe.
-  if (!ctx || !poses7 || !ms_per_launch || n < 1 || n > kMaxBatchExt || repeats < 1) return NID_ERR_INVALID_ARG;
-  NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-  for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
   Pose p[kMaxBatchExt];
-  for (int k = 0; k < n; k++) pose_from_pose7(poses7 + 7 * k, ctx->xform, &p[k]);
+  double *target = nullptr;
+  { int rc = time_prepare(ctx, n, poses7, ms_per_launch, repeats, p, &target); if (rc) return rc; }
   Slot &S0 = ctx->slots[0];
   { int rc = timing_events(ctx, S0); if (rc) return rc; }
   // (nid_enable_timing would make launch_batch record the slot's e0 / e1 around every repeat: off for the duration)
   struct TimingOff { nid_ctx *c; bool was; ~TimingOff() { c->timing = was; } } timing_off{ctx, ctx->timing};
   ctx->timing = false;
-  // launches of more than kMaxBatch poses are what the pipelined loop issues: they write their result blocks to a
-  // device buffer like there (nid_run_sequence); smaller ones to pinned host memory like the blocking calls
-  double *target = nullptr;
-  if (n > kMaxBatch) {
-    int rc = ensure_seq_ring(ctx, n);
-    if (rc) return rc;
-    target = ctx->seq_dev[0];
-  }
   NID_HIP(ctx, hipEventRecord(S0.e0, ctx->stream));
   for (int r = 0; r < repeats; r++) {
     // (never DIRECT: the launches are re-issued into the same buffers before the host has looked)
@@ -2300,19 +2281,11 @@ int nid_time_kernel(nid_ctx *ctx, int n, const double *poses7, int want_jac, dou
   // The evaluation kernel ALONE: every repeat is one n-pose launch with an event right in front of k_eval2 (behind the in-stream
   // copy of the per-pose records) and one right behind it (in front of k_repair), awaited before the next -- what a kernel trace
   // reports for that kernel (nid_time_launches brackets whole launches back to back: copy + k_eval2 + k_repair + dispatch gaps).
-  if (!ctx || !poses7 || !ms_kernel || n < 1 || n > kMaxBatchExt || repeats < 1) return NID_ERR_INVALID_ARG;
-  NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-  for (int s = 0; s < NID_SLOTS; s++) if (ctx->slots[s].pending) return NID_ERR_STATE;
   Pose p[kMaxBatchExt];
-  for (int k = 0; k < n; k++) pose_from_pose7(poses7 + 7 * k, ctx->xform, &p[k]);
+  double *target = nullptr;
+  { int rc = time_prepare(ctx, n, poses7, ms_kernel, repeats, p, &target); if (rc) return rc; }
   struct TimingOn { nid_ctx *c; bool was; ~TimingOn() { c->timing = was; } } timing_on{ctx, ctx->timing};
   ctx->timing = true;
-  double *target = nullptr;
-  if (n > kMaxBatch) {
-    int rc = ensure_seq_ring(ctx, n);
-    if (rc) return rc;
-    target = ctx->seq_dev[0];
-  }
   double sum = 0.0;
   for (int r = 0; r < repeats; r++) {
     int rc = launch_batch(ctx, 0, n, p, want_jac, delta, target, false, /*relaunch_ok=*/false, /*allow_direct=*/false);

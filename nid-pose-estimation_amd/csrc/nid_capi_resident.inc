@@ -258,7 +258,7 @@ int resident_fallback(nid_ctx *ctx, Slot &S) {
   EvalParams P{};
   fill_common_params(ctx, 1.0, &P);
   SlotArgs &A = P.slot[0];
-  fill_slot_args(R.pose, S, nullptr, nullptr, &A);
+  fill_slot_args(ctx, R.pose, S, nullptr, nullptr, &A);
   A.quad = S.quad_host_devptr;
   A.host_quad = R.want_cellout ? 2 : 1;
   S.quad_dirty = !R.want_cellout;

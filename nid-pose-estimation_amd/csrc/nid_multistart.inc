@@ -5,8 +5,8 @@
 // per-pose records live in a device array of the call's own for EVERY n (launches of <= kMaxBatch poses normally carry
 // them in the kernel arguments, which would not see the poses k_lm_step writes): the EXT instantiations of the 128- /
 // 256-thread kernels, whatever n is, so a chain gives the same bits alone and beside 255 others.  Each chain owns its
-// per-cell blocks, group sums, tickets (zero between grids, as the kernels leave them) and result block -- a private
-// pool like the fused pipeline's; the public slots are neither used nor marked.
+// per-cell blocks, group sums, tickets (zero between grids, as the kernels leave them), its record -- a PosePool of the
+// call's own, like the fused pipeline's -- and its result block; the public slots are neither used nor marked.
 // k_lm_step runs lm_step() of nid_lm_step.h for every chain on the block its pose just produced (k_repair is in front
 // of it in the stream: a repaired cell's contribution is in), writes the chain's state and the `pose` member of its
 // record, one trace record if asked, and adds the chains that are still running to the round's word.  A finished chain
@@ -54,9 +54,9 @@ __global__ void __launch_bounds__(64) k_lm_step(const MsStepArgs A) {
 
 void free_ms_pool(nid_ctx *ctx) {
   nid_ctx::MsPool &Q = ctx->ms;
-  (void)hipFree(Q.quad); (void)hipFree(Q.gpart); (void)hipFree(Q.ticket); (void)hipFree(Q.rec_dev); (void)hipFree(Q.reduced);
-  (void)hipFree(Q.state_dev); (void)hipFree(Q.running_dev); (void)hipFree(Q.trace_dev);
-  if (Q.stage) (void)hipHostFree(Q.stage);
+  pool_free(Q.poses);
+  (void)hipFree(Q.reduced); (void)hipFree(Q.state_dev); (void)hipFree(Q.running_dev); (void)hipFree(Q.trace_dev);
+  if (Q.state_host) (void)hipHostFree(Q.state_host);
   if (Q.running_host) (void)hipHostFree(Q.running_host);
   Q = nid_ctx::MsPool();
 }
@@ -64,7 +64,6 @@ void free_ms_pool(nid_ctx *ctx) {
 // buffers for `chains` chains and `rounds` rounds (grow only; the trace only when asked for)
 int ensure_ms_pool(nid_ctx *ctx, int chains, int rounds, bool trace) {
   nid_ctx::MsPool &Q = ctx->ms;
-  const size_t n_ticket = seq_ticket_words(ctx);
   if (Q.chains < chains) {
     resident_retire(ctx);  // (hipFree waits for the whole device)
     const int r_keep = Q.rounds;
@@ -72,15 +71,10 @@ int ensure_ms_pool(nid_ctx *ctx, int chains, int rounds, bool trace) {
     rounds = std::max(rounds, r_keep);
     const size_t n = (size_t)chains;
     int rc;
-    if ((rc = dev_alloc(ctx, &Q.quad, n * ctx->g.nloc * kQuad))) return rc;
-    if ((rc = dev_alloc(ctx, &Q.gpart, n * ctx->ngroups * kQuad))) return rc;
-    if ((rc = dev_alloc(ctx, &Q.ticket, n * n_ticket))) return rc;
-    NID_HIP(ctx, hipMemset(Q.ticket, 0, n * n_ticket * sizeof(unsigned)));  // (the kernels leave them zero behind every grid)
-    if ((rc = dev_alloc(ctx, &Q.rec_dev, n))) return rc;
+    if ((rc = pool_ensure(ctx, Q.poses, n, true))) return rc;
     if ((rc = dev_alloc(ctx, &Q.reduced, n * kReducedLen))) return rc;
     if ((rc = dev_alloc(ctx, &Q.state_dev, n))) return rc;
-    Q.stage_bytes = n * (sizeof(SlotArgs) + sizeof(nid_ms_state));
-    if (hipHostMalloc(reinterpret_cast<void **>(&Q.stage), Q.stage_bytes, hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
+    if (hipHostMalloc(reinterpret_cast<void **>(&Q.state_host), n * sizeof(nid_ms_state), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
     Q.chains = chains;
   }
   if (Q.rounds < rounds) {
@@ -130,8 +124,7 @@ int nid_multistart_lm(nid_ctx *ctx, const double *poses7_in, int n, int iteratio
   if (iterations > (1 << 20)) return NID_ERR_INVALID_ARG;
   int rc = check_ready(ctx);
   if (rc) return rc;
-  for (int s = 0; s < NID_SLOTS; s++)
-    if (ctx->slots[s].pending) { ctx->last_error = "a launch is pending: nid_wait() it first"; return NID_ERR_STATE; }
+  if (any_pending(ctx)) { ctx->last_error = "a launch is pending: nid_wait() it first"; return NID_ERR_STATE; }
   if (ctx->dbg_enabled || ctx->dbg_stamps) { ctx->last_error = "nid_multistart_lm: switch the per-pixel dump / phase stamps off"; return NID_ERR_STATE; }
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   const int rounds_cap = max_rounds > 0 ? max_rounds : 1 + lm::kMaxTrials * iterations;
@@ -139,42 +132,32 @@ int nid_multistart_lm(nid_ctx *ctx, const double *poses7_in, int n, int iteratio
   nid_ctx::MsPool &Q = ctx->ms;
   hipStream_t st = ctx->stream;
 
-  // records and states of the start poses: pinned mirror, one copy each
-  SlotArgs *rec_host = reinterpret_cast<SlotArgs *>(Q.stage);
-  nid_ms_state *state_host = reinterpret_cast<nid_ms_state *>(Q.stage + (size_t)Q.chains * sizeof(SlotArgs));
-  const size_t n_quad = (size_t)ctx->g.nloc * kQuad, n_gpart = (size_t)ctx->ngroups * kQuad, n_ticket = seq_ticket_words(ctx);
+  // records and states of the start poses: pinned mirrors, one copy each (the records': with the first grid, below)
+  nid_ms_state *state_host = Q.state_host;
   for (int k = 0; k < n; k++) {
     nid_ms_state &S = state_host[k];
     lm::lm_init(&S, poses7_in + 7 * (size_t)k, iterations, ctx->xform);
-    SlotArgs &A = rec_host[k];
+    SlotArgs &A = Q.poses.rec_host[k];
+    pool_record(ctx, Q.poses, (size_t)k, Q.reduced + (size_t)k * kReducedLen, &A);
     for (int i = 0; i < 7; i++) A.pose.q[i] = S.rec_q[i];
     for (int i = 0; i < 12; i++) A.pose.M[i] = S.rec_M[i];
     A.pose.mode = S.rec_mode;
-    A.cellout = nullptr;  // nobody reads the per-cell outputs
-    A.quad = Q.quad + k * n_quad;
-    A.gpart = Q.gpart + k * n_gpart;
-    A.ticket = Q.ticket + k * n_ticket;
-    A.out_reduced = Q.reduced + (size_t)k * kReducedLen;
-    A.host_seq = nullptr;
-    A.launch_seq = 0;
-    A.cellout_host = 0;
-    A.host_quad = 0;
   }
-  NID_HIP(ctx, hipMemcpyAsync(Q.rec_dev, rec_host, (size_t)n * sizeof(SlotArgs), hipMemcpyHostToDevice, st));
   NID_HIP(ctx, hipMemcpyAsync(Q.state_dev, state_host, (size_t)n * sizeof(nid_ms_state), hipMemcpyHostToDevice, st));
   NID_HIP(ctx, hipMemsetAsync(Q.running_dev, 0, (size_t)rounds_cap * sizeof(unsigned), st));
 
   EvalParams P{};
   fill_common_params(ctx, delta, &P);
-  P.slots_ext = Q.rec_dev;  // for every n: see the head of this file (pick_threads keeps such a grid at <= 256 threads)
   const int chunk = ms_chunk(n);
   int enqueued = 0, done = -1;  // done: rounds until the last chain finished
   auto drain = [&]() { (void)hipStreamSynchronize(st); };  // (an error must not leave grids of this call behind)
   while (enqueued < rounds_cap && done < 0) {
     const int upto = std::min(rounds_cap, enqueued + chunk);
     for (int r = enqueued; r < upto; r++) {
-      if ((rc = launch_eval2(ctx, P, true, st, n))) { drain(); return rc; }
-      MsStepArgs A{Q.state_dev, Q.rec_dev, Q.reduced, trace ? Q.trace_dev + (size_t)r * n : nullptr, Q.running_dev + r, n};
+      // records on the device for every n: see the head of this file (launch_eval2 keeps such a grid at <= 256 threads);
+      // ONE upload, with the call's first grid -- k_lm_step keeps the poses there up to date
+      if ((rc = launch_records(ctx, P, r == 0 ? Q.poses.rec_host : nullptr, n, Q.poses.rec_dev, true, true, st))) { drain(); return rc; }
+      MsStepArgs A{Q.state_dev, Q.poses.rec_dev, Q.reduced, trace ? Q.trace_dev + (size_t)r * n : nullptr, Q.running_dev + r, n};
       hipLaunchKernelGGL(k_lm_step, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, A);
     }
     if (hipGetLastError() != hipSuccess) { drain(); ctx->last_error = "k_lm_step launch failed"; return NID_ERR_HIP;}

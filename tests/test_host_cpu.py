@@ -382,3 +382,15 @@ def test_direct_results_avx512_sums_equal_the_scalar_loop(tmp_path, compiler):
     if r.returncode == 2:
         pytest.skip("no AVX-512 on this CPU: the library takes the scalar loop here")
     assert r.returncode == 0, r.stdout[-2000:]
+
+
+def test_fused_grid_budget_rule_matches_hand_derived_values(tmp_path):
+    """csrc/nid_pose_pool.h (per-pose buffer sizes, and how many batches nid_run_sequence fuses into one grid with how many
+    grids in flight: plain arithmetic, no HIP) against tests/cpp/pose_pool_check.cpp's table, derived by hand from the rule's
+    comment for a 224-byte record, and its invariants: F >= 1, 2 to 4 grids in flight, two grids within 2^30 bytes
+    whenever F > 1.  tests/test_fused_sequence_gpu.py runs the pipeline itself."""
+    exe = str(tmp_path / "pose_pool_check")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "nid-pose-estimation_amd", "csrc"),
+                           "-o", exe, os.path.join(ROOT, "tests", "cpp", "pose_pool_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "pose pool rule ok" in r.stdout, r.stdout[-2000:]
