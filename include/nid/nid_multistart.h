@@ -26,7 +26,8 @@
  *
  * Out of scope: cell shards over several GPUs (nid_multi.h contexts: use one context that owns all cells), more
  * than NID_MAX_BATCH = 256 chains per call, and compacting finished chains out of the grid (a finished chain's
- * pose is still evaluated every round until the last chain ends; its blocks are ignored).
+ * pose is still evaluated every round until the last chain ends; its blocks are ignored).  Chains over the levels of
+ * an image pyramid, coarse to fine: include/nid/nid_pyr.h.
  */
 #ifndef NID_MULTISTART_H
 #define NID_MULTISTART_H

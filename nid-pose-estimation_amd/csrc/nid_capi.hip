@@ -22,10 +22,11 @@
 
 #include "nid/nid_c.h"
 #include "nid/nid_multistart.h"
+#include "nid/nid_pyr.h"
 #include "nid_eval_launch.h"
 #include "nid_pose_pool.h"             // pose_sizes, seq_fusion: per-pose buffer sizes and the fused grids' budget rule (no HIP in it)
 #include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
-#include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
+#include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_pyr_down, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
 
 using namespace nid;
@@ -1212,12 +1213,12 @@ PairStage pair_stage_layout(const Geometry &g) {
   return L;
 }
 
-int pair_u16_enqueue(nid_ctx *ctx, const uint16_t *depth_u16, double depth_factor, const uint8_t *im0, const uint8_t *im1,
-                     const double *Twc, const Pose &pose0) {
+// pair_u16_enqueue in two parts (nid_pyr.inc runs the second for every pyramid level, the first for level 0 only).
+// UPLOAD: the pair through the context's pinned block onto `st` -- depth16_dev, im0_dev, im1_dev, Twc_dev.
+int pair_u16_upload(nid_ctx *ctx, const uint16_t *depth_u16, const uint8_t *im0, const uint8_t *im1, const double *Twc, hipStream_t stream) {
   const Geometry &g = ctx->g;
   const size_t N = (size_t)g.rows * g.cols;
   const PairStage L = pair_stage_layout(g);
-  resident_retire(ctx);
   if (!ctx->depth16_dev) NID_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->depth16_dev), N * sizeof(uint16_t)));
   if (!ctx->pair_stage && hipHostMalloc(reinterpret_cast<void **>(&ctx->pair_stage), L.bytes, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError(); ctx->pair_stage = nullptr; return NID_ERR_NOMEM;
@@ -1227,17 +1228,36 @@ int pair_u16_enqueue(nid_ctx *ctx, const uint16_t *depth_u16, double depth_facto
   std::memcpy(st + L.im0, im0, N);
   std::memcpy(st + L.im1, im1, N);
   std::memcpy(st + L.twc, Twc, 16 * sizeof(double));
-  NID_HIP(ctx, hipMemcpyAsync(ctx->depth16_dev, st + L.depth, 2 * N, hipMemcpyHostToDevice, ctx->stream));
-  NID_HIP(ctx, hipMemcpyAsync(ctx->im0_dev, st + L.im0, N, hipMemcpyHostToDevice, ctx->stream));
-  NID_HIP(ctx, hipMemcpyAsync(ctx->im1_dev, st + L.im1, N, hipMemcpyHostToDevice, ctx->stream));
-  NID_HIP(ctx, hipMemcpyAsync(ctx->Twc_dev, st + L.twc, 16 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_depth_u16, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, (long)N, ctx->depth16_dev, depth_factor, ctx->depth_dev);
+  NID_HIP(ctx, hipMemcpyAsync(ctx->depth16_dev, st + L.depth, 2 * N, hipMemcpyHostToDevice, stream));
+  NID_HIP(ctx, hipMemcpyAsync(ctx->im0_dev, st + L.im0, N, hipMemcpyHostToDevice, stream));
+  NID_HIP(ctx, hipMemcpyAsync(ctx->im1_dev, st + L.im1, N, hipMemcpyHostToDevice, stream));
+  NID_HIP(ctx, hipMemcpyAsync(ctx->Twc_dev, st + L.twc, 16 * sizeof(double), hipMemcpyHostToDevice, stream));
+  return NID_OK;
+}
+
+// DEVICE: from depth16_dev, im0_dev, im1_dev and Twc_dev on `stream`: depth -> metres, back-projection + tiling, the
+// target's margins.  Launches only: the caller asks hipGetLastError behind its last launch.
+void pair_u16_device(nid_ctx *ctx, double depth_factor, hipStream_t stream) {
+  const Geometry &g = ctx->g;
+  const size_t N = (size_t)g.rows * g.cols;
+  hipLaunchKernelGGL(k_depth_u16, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (long)N, ctx->depth16_dev, depth_factor, ctx->depth_dev);
   const long total = (long)g.nloc * g.pstride;
-  hipLaunchKernelGGL(k_tile, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, g, ctx->depth_dev,
+  hipLaunchKernelGGL(k_tile, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, g, ctx->depth_dev,
                      (const double *)nullptr, ctx->im0_dev, ctx->Twc_dev, ctx->t, (double *)nullptr);
   const long mtotal = (long)(g.rows + 1) * (g.cols + 1);
-  hipLaunchKernelGGL(k_im1_margins, dim3((unsigned)((mtotal + 255) / 256)), dim3(256), 0, ctx->stream, g.rows, g.cols,
+  hipLaunchKernelGGL(k_im1_margins, dim3((unsigned)((mtotal + 255) / 256)), dim3(256), 0, stream, g.rows, g.cols,
                      ctx->im1_stride, ctx->im1_dev, ctx->im1s_dev);
+}
+
+int pair_u16_enqueue(nid_ctx *ctx, const uint16_t *depth_u16, double depth_factor, const uint8_t *im0, const uint8_t *im1,
+                     const double *Twc, const Pose &pose0) {
+  const Geometry &g = ctx->g;
+  const PairStage L = pair_stage_layout(g);
+  resident_retire(ctx);
+  int rc = pair_u16_upload(ctx, depth_u16, im0, im1, Twc, ctx->stream);
+  if (rc) return rc;
+  uint8_t *st = ctx->pair_stage;
+  pair_u16_device(ctx, depth_factor, ctx->stream);
   hipLaunchKernelGGL((k_href<256>), dim3(g.nloc), dim3(256), 0, ctx->stream, g, pose0, ctx->t, ctx->Nc_dev, ctx->Href_dev,
                      ctx->hist_scale, ctx->hist_inv_scale);
   NID_HIP(ctx, hipGetLastError());
@@ -2316,3 +2336,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- many LM chains at once, stepped on the device (include/nid/nid_multistart.h) ---
 #include "nid_multistart.inc"
+
+// ---- a device-built resident pyramid and coarse-to-fine multi-start LM on it (include/nid/nid_pyr.h) ---
+#include "nid_pyr.inc"

@@ -1,0 +1,207 @@
+// nid_pyr.inc -- a device-built, resident image pyramid and the coarse-to-fine loop over its levels (include/nid/nid_pyr.h).
+// Part of nid_capi.hip's translation unit (included behind nid_multistart.inc): it works on the level contexts' internals.
+//
+// A level is an ordinary context from nid_create(nid_pyr_level_config(...)).  nid_pyr_set_pair_u16 enqueues EVERYTHING --
+// level 0's uploads (pair_u16_upload), levels - 1 k_pyr_down launches, every level's set-up chain (pair_u16_device) -- on
+// ONE stream, level 0's, in dependency order, and synchronises it once before it marks any level ready: a level's later
+// launches run on that level's own streams, and nothing of this call is in flight by then.  What a level's own streams may
+// still be running when the call begins (k_repair behind a collected launch) is put in front of it with one event per
+// stream, on the device.  nid_pyr_multistart_lm calls nid_compute_href and nid_multistart_lm as they are: it fills no
+// record and launches nothing of its own; the survivors of a level are a handful of comparisons on the host.
+
+struct nid_pyr {
+  int levels = 0;
+  nid_ctx *ctx[NID_PYR_MAX_LEVELS] = {};
+  hipEvent_t idle[NID_PYR_MAX_LEVELS][2] = {};  // a level's stream / aux_stream have reached this call
+  bool have_pair = false;
+};
+
+namespace {
+
+int pyr_fail(nid_pyr *p, int rc, const std::string &why) {
+  p->ctx[0]->last_error = why;
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nid_pyr_level_config(const nid_config *cfg0, int level, nid_config *out) {
+  if (!cfg0 || !out || level < 0 || level >= NID_PYR_MAX_LEVELS) return NID_ERR_INVALID_ARG;
+  if (cfg0->cell_begin != 0 || cfg0->cell_end != 0) return NID_ERR_INVALID_ARG;  // shards are out of scope
+  if (cfg0->rows < 1 || cfg0->cols < 1 || cfg0->cell_num < 1) return NID_ERR_INVALID_ARG;
+  const int d = 1 << level;  // (the rule of nid_host_run_pyramid_lm)
+  if ((cfg0->rows % d) || (cfg0->cols % d) || (cfg0->cell_num % d) || (cfg0->cell_num >> level) < 1) return NID_ERR_INVALID_ARG;
+  nid_config c = *cfg0;
+  for (int l = 0; l < level; l++) {  // host/nid_pyramid.cpp's operations, in its order
+    c.rows = c.rows / 2; c.cols = c.cols / 2; c.cell_num = c.cell_num / 2;
+    c.fx = c.fx / 2; c.fy = c.fy / 2; c.cx = (c.cx - 0.5) / 2; c.cy = (c.cy - 0.5) / 2;
+  }
+  *out = c;
+  return NID_OK;
+}
+
+int nid_pyr_destroy(nid_pyr *p) {
+  if (!p) return NID_OK;
+  for (int l = 0; l < p->levels; l++) {
+    if (p->ctx[l]) (void)hipSetDevice(p->ctx[l]->cfg.device);
+    for (hipEvent_t e : p->idle[l]) if (e) (void)hipEventDestroy(e);
+    (void)nid_destroy(p->ctx[l]);
+  }
+  delete p;
+  return NID_OK;
+}
+
+int nid_pyr_create(const nid_config *cfg0, int levels, nid_pyr **out) {
+  if (!cfg0 || !out) return NID_ERR_INVALID_ARG;
+  *out = nullptr;
+  if (levels < 1 || levels > NID_PYR_MAX_LEVELS) return NID_ERR_INVALID_ARG;
+  nid_config c;
+  int rc = nid_pyr_level_config(cfg0, levels - 1, &c);
+  if (rc) return rc;
+  nid_pyr *p = new (std::nothrow) nid_pyr();
+  if (!p) return NID_ERR_NOMEM;
+  p->levels = levels;
+  auto fail = [&](int code) { nid_pyr_destroy(p); return code; };
+  for (int l = 0; l < levels; l++) {
+    if ((rc = nid_pyr_level_config(cfg0, l, &c))) return fail(rc);
+    if ((rc = nid_create(&c, &p->ctx[l]))) return fail(rc);
+    // (here, not on the first pair: hipMalloc waits for the whole device)
+    nid_ctx *ctx = p->ctx[l];
+    if ((rc = dev_alloc(ctx, &ctx->depth16_dev, (size_t)c.rows * c.cols))) return fail(rc);
+    for (hipEvent_t &e : p->idle[l])
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
+  }
+  *out = p;
+  return NID_OK;
+}
+
+int nid_pyr_levels(const nid_pyr *p) { return p ? p->levels : 0; }
+
+nid_ctx *nid_pyr_level(nid_pyr *p, int level) { return (p && level >= 0 && level < p->levels) ? p->ctx[level] : nullptr; }
+
+int nid_pyr_set_pair_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, const uint8_t *im0, const uint8_t *im1,
+                         const double *Twc) {
+  if (!p || !depth_u16 || !im0 || !im1 || !Twc) return NID_ERR_INVALID_ARG;
+  for (int l = 0; l < p->levels; l++)
+    if (any_pending(p->ctx[l])) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_set_pair_u16: a launch is pending on level " + std::to_string(l) + ": nid_wait() it first");
+  // from here on the levels are being overwritten: none of them is ready until the stream has drained
+  p->have_pair = false;
+  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_target = p->ctx[l]->have_href = false;
+  nid_ctx *c0 = p->ctx[0];
+  NID_HIP(c0, hipSetDevice(c0->cfg.device));
+  for (int l = 0; l < p->levels; l++) resident_retire(p->ctx[l]);
+  const hipStream_t st = c0->stream;
+  // what the levels' own streams still run reads the buffers this call rewrites: in front of it, on the device
+  for (int l = 0; l < p->levels; l++) {
+    nid_ctx *ctx = p->ctx[l];
+    const hipStream_t own[2] = {ctx->stream, ctx->aux_stream};
+    for (int s = 0; s < 2; s++) {
+      if (!own[s] || own[s] == st) continue;
+      NID_HIP(c0, hipEventRecord(p->idle[l][s], own[s]));
+      NID_HIP(c0, hipStreamWaitEvent(st, p->idle[l][s], 0));
+    }
+  }
+  auto drain = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };  // (an error leaves nothing of this call in flight)
+  int rc = pair_u16_upload(c0, depth_u16, im0, im1, Twc, st);
+  if (rc) return drain(rc);
+  const PairStage L0 = pair_stage_layout(c0->g);
+  for (int l = 1; l < p->levels; l++) {
+    nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
+    if (hipMemcpyAsync(dst->Twc_dev, c0->pair_stage + L0.twc, 16 * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
+      return drain(pyr_fail(p, NID_ERR_HIP, "nid_pyr_set_pair_u16: hipMemcpyAsync(T_wc0)"));
+    const int rows2 = dst->g.rows, cols2 = dst->g.cols;
+    const long threads = (long)rows2 * ((cols2 + kPyrRun - 1) / kPyrRun);
+    hipLaunchKernelGGL(k_pyr_down, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, rows2, cols2, src->im0_dev, src->im1_dev,
+                       src->depth16_dev, depth_factor, dst->im0_dev, dst->im1_dev, dst->depth16_dev);
+  }
+  for (int l = 0; l < p->levels; l++) pair_u16_device(p->ctx[l], depth_factor, st);
+  {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return drain(pyr_fail(p, NID_ERR_HIP, std::string("nid_pyr_set_pair_u16: a launch failed: ") + hipGetErrorString(e)));
+  }
+  NID_HIP(c0, hipStreamSynchronize(st));
+  for (int l = 0; l < p->levels; l++) {
+    nid_ctx *ctx = p->ctx[l];
+    ctx->have_ref = ctx->have_target = true;  // (have_href stays false: the reference stage is the caller's)
+    ctx->ref_from_depth = true;
+  }
+  p->have_pair = true;
+  return NID_OK;
+}
+
+int nid_pyr_get_level_inputs(nid_pyr *p, int level, uint16_t *depth_u16, uint8_t *im0, uint8_t *im1) {
+  if (!p || level < 0 || level >= p->levels) return NID_ERR_INVALID_ARG;
+  nid_ctx *ctx = p->ctx[level];
+  if (!p->have_pair) { ctx->last_error = "nid_pyr_get_level_inputs: no pair set"; return NID_ERR_STATE; }
+  NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
+  resident_retire(ctx);
+  const size_t N = (size_t)ctx->g.rows * ctx->g.cols;
+  if (depth_u16) NID_HIP(ctx, hipMemcpyAsync(depth_u16, ctx->depth16_dev, N * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (im0) NID_HIP(ctx, hipMemcpyAsync(im0, ctx->im0_dev, N, hipMemcpyDeviceToHost, ctx->stream));
+  if (im1) NID_HIP(ctx, hipMemcpyAsync(im1, ctx->im1_dev, N, hipMemcpyDeviceToHost, ctx->stream));
+  NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return NID_OK;
+}
+
+int nid_pyr_multistart_lm(nid_pyr *p, const double *poses7_in, int n, const double *pose_ref7, int iterations, double delta,
+                          const int32_t *keep, nid_ms_result *results, int32_t *origin, int32_t *rounds, int *best_origin,
+                          double *best_pose7) {
+  if (!p || !poses7_in || !results || !origin || n < 1 || n > kMaxBatchExt || iterations < 1) return NID_ERR_INVALID_ARG;
+  const int L = p->levels;
+  int kp[NID_PYR_MAX_LEVELS];
+  for (int l = 0; l < L; l++) kp[l] = keep ? keep[l] : n;
+  if (kp[L - 1] != n) return pyr_fail(p, NID_ERR_INVALID_ARG, "nid_pyr_multistart_lm: keep[levels-1] must be n");
+  for (int l = 0; l + 1 < L; l++)
+    if (kp[l] < 1 || kp[l] > kp[l + 1]) return pyr_fail(p, NID_ERR_INVALID_ARG, "nid_pyr_multistart_lm: 1 <= keep[l] <= keep[l+1]");
+  if (!p->have_pair) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_multistart_lm: no pair set");
+  for (int l = 0; l < L; l++)
+    if (any_pending(p->ctx[l])) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_multistart_lm: a launch is pending on level " + std::to_string(l) + ": nid_wait() it first");
+  std::memset(results, 0, (size_t)L * n * sizeof(nid_ms_result));
+  std::fill(origin, origin + (size_t)L * n, (int32_t)-1);
+  if (rounds) std::fill(rounds, rounds + L, (int32_t)0);
+  if (best_origin) *best_origin = -1;
+
+  std::vector<double> cur(poses7_in, poses7_in + 7 * (size_t)n), next;
+  std::vector<int32_t> cur_origin(n), next_origin;
+  for (int k = 0; k < n; k++) cur_origin[k] = k;
+  std::vector<int> order;
+  int m = n;  // chains of the running level
+  for (int l = L - 1; l >= 0; l--) {
+    nid_ctx *ctx = p->ctx[l];
+    nid_ms_result *res = results + (size_t)(L - 1 - l) * n;
+    auto failed = [&](int rc) { if (l) p->ctx[0]->last_error = "level " + std::to_string(l) + ": " + ctx->last_error; return rc; };
+    int rc = nid_compute_href(ctx, (l == L - 1 && pose_ref7) ? pose_ref7 : cur.data(), nullptr, nullptr, nullptr, nullptr);
+    if (rc) return failed(rc);
+    int r = 0;
+    if ((rc = nid_multistart_lm(ctx, cur.data(), m, iterations, delta, 0, res, nullptr, nullptr, &r))) return failed(rc);
+    if (rounds) rounds[L - 1 - l] = r;
+    std::copy(cur_origin.begin(), cur_origin.begin() + m, origin + (size_t)(L - 1 - l) * n);
+    // the eligible chains by chi2 / n_active ascending, the lower index winning ties (the rule of nid_multistart_lm's *best)
+    order.clear();
+    for (int k = 0; k < m; k++)
+      if (res[k].n_active > 0 && std::isfinite(res[k].chi2)) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+      return res[a].chi2 / (double)res[a].n_active < res[b].chi2 / (double)res[b].n_active;
+    });
+    if (order.empty()) return NID_OK;  // (*best_origin is -1, the finer levels' rows are zero)
+    if (l == 0) {
+      if (best_origin) *best_origin = cur_origin[order[0]];
+      if (best_pose7) std::memcpy(best_pose7, res[order[0]].pose7, 7 * sizeof(double));
+      break;
+    }
+    m = std::min(kp[l - 1], (int)order.size());
+    next.resize(7 * (size_t)m);
+    next_origin.resize(m);
+    for (int k = 0; k < m; k++) {
+      std::memcpy(next.data() + 7 * (size_t)k, res[order[k]].pose7, 7 * sizeof(double));
+      next_origin[k] = cur_origin[order[k]];
+    }
+    cur.swap(next);
+    cur_origin.swap(next_origin);
+  }
+  return NID_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // nid_setup_kernels.hip.h -- the once-per-pair kernels: back-projection + tiling, the target image's margins, the reference
-// stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs.
+// stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
+// next pyramid level (k_pyr_down).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
@@ -83,6 +84,72 @@ __global__ void k_im1_margins(int rows, int cols, int stride, const uint8_t *__r
   else if (c >= 0) v = rows > 1 ? 2 * at(0, c) - at(1, c) : at(0, c);
   else v = rows > 1 ? 2 * col_m1(0) - col_m1(1) : col_m1(0);  // corner: never read with a non-zero weight
   dst[(size_t)(r + 1) * stride + (c + 1)] = (int16_t)v;
+}
+
+// Pyramid level l+1 from level l on the device (nid_pyr.h): all three planes in one launch, the arithmetic of
+// nid_pyr_down_u8 / nid_pyr_down_depth_u16 (host/nid_pyramid.cpp) operation for operation -- images (a + b + c + d + 2) >> 2;
+// depth: the mean of the VALID samples (metres = (double)count * factor, one IEEE product, valid as in k_tile) rounded
+// half up in unsigned integers, 0 if none is valid -- so the planes are the host's, byte for byte.  The source is
+// (2 rows2) x (2 cols2).  One thread makes kPyrRun adjacent output pixels of every plane: 8 source bytes of two image
+// rows, 16 of two depth rows, one 4-byte and one 8-byte store per plane; the last pixels of a row whose width is no
+// multiple of kPyrRun are made one by one.  Rows of a level are cols2 elements apart -- a multiple of nothing --, so every
+// wide access goes through memcpy with the element's alignment and the compiler picks the instruction.
+constexpr int kPyrRun = 4;
+__device__ inline uint16_t pyr_depth_mean(const uint16_t v[4], double factor) {
+  unsigned sum = 0, n = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const double z = (double)v[k] * factor;
+    if (!(z < 0.01 || z > 100)) { sum += v[k]; n++; }
+  }
+  return n ? (uint16_t)((2 * sum + n) / (2 * n)) : (uint16_t)0;
+}
+
+__global__ void __launch_bounds__(256) k_pyr_down(int rows2, int cols2, const uint8_t *__restrict__ im0, const uint8_t *__restrict__ im1,
+                                                  const uint16_t *__restrict__ depth, double factor, uint8_t *__restrict__ o_im0,
+                                                  uint8_t *__restrict__ o_im1, uint16_t *__restrict__ o_depth) {
+  const int runs = (cols2 + kPyrRun - 1) / kPyrRun;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)rows2 * runs) return;
+  const int r = (int)(gid / runs), c0 = (int)(gid % runs) * kPyrRun;
+  const size_t cols = 2 * (size_t)cols2;
+  const size_t top = (size_t)(2 * r) * cols + 2 * (size_t)c0;  // source: rows 2r and 2r + 1, from column 2 c0
+  const size_t out = (size_t)r * cols2 + c0;
+  if (c0 + kPyrRun <= cols2) {
+    auto box4 = [](const uint8_t *a, const uint8_t *b) {
+      unsigned long long ra, rb;
+      __builtin_memcpy(&ra, a, 8);
+      __builtin_memcpy(&rb, b, 8);
+      unsigned o = 0;
+#pragma unroll
+      for (int k = 0; k < kPyrRun; k++) {
+        const unsigned s = (unsigned)((ra >> (16 * k)) & 0xff) + (unsigned)((ra >> (16 * k + 8)) & 0xff) +
+                           (unsigned)((rb >> (16 * k)) & 0xff) + (unsigned)((rb >> (16 * k + 8)) & 0xff);
+        o |= ((s + 2) >> 2) << (8 * k);
+      }
+      return o;
+    };
+    const unsigned p0 = box4(im0 + top, im0 + top + cols), p1 = box4(im1 + top, im1 + top + cols);
+    __builtin_memcpy(o_im0 + out, &p0, 4);
+    __builtin_memcpy(o_im1 + out, &p1, 4);
+    uint16_t da[2 * kPyrRun], db[2 * kPyrRun], od[kPyrRun];
+    __builtin_memcpy(da, depth + top, sizeof(da));
+    __builtin_memcpy(db, depth + top + cols, sizeof(db));
+#pragma unroll
+    for (int k = 0; k < kPyrRun; k++) {
+      const uint16_t v[4] = {da[2 * k], da[2 * k + 1], db[2 * k], db[2 * k + 1]};
+      od[k] = pyr_depth_mean(v, factor);
+    }
+    __builtin_memcpy(o_depth + out, od, sizeof(od));
+  } else {
+    for (int k = 0; c0 + k < cols2; k++) {
+      const size_t s = top + 2 * (size_t)k;
+      o_im0[out + k] = (uint8_t)((im0[s] + im0[s + 1] + im0[s + cols] + im0[s + cols + 1] + 2) >> 2);
+      o_im1[out + k] = (uint8_t)((im1[s] + im1[s + 1] + im1[s + cols] + im1[s + cols + 1] + 2) >> 2);
+      const uint16_t v[4] = {depth[s], depth[s + 1], depth[s + cols], depth[s + cols + 1]};
+      o_depth[out + k] = pyr_depth_mean(v, factor);
+    }
+  }
 }
 
 // depth pixels that belong to no cell (rows/cols not divisible by cell_num, Q11)

@@ -18,9 +18,31 @@
 static double g_last_optimize_s = 0.0;
 double nid_host_last_optimize_seconds(void) { return g_last_optimize_s; }
 
-void nid_host_set_devices(const int32_t *devices, int n, int reduce_rccl) { nid_legacy_set_devices(devices, n, reduce_rccl); }
+// What this layer was told about devices, ranks and launch shapes, for nid_host_run_pyramid_multistart_lm: its level
+// contexts are a nid_pyr's, not the operators', and the operators keep their settings to themselves.
+static int g_host_devices = 1, g_host_device0 = 0, g_host_world = 1;
+static int g_host_jac_threads = -1, g_host_cost_threads = 0;
+void nid_host_configured(int *devices, int *device0, int *world, int *jac_threads, int *cost_threads) {
+  if (devices) *devices = g_host_devices;
+  if (device0) *device0 = g_host_device0;
+  if (world) *world = g_host_world;
+  if (jac_threads) *jac_threads = g_host_jac_threads;
+  if (cost_threads) *cost_threads = g_host_cost_threads;
+}
+
+void nid_host_set_devices(const int32_t *devices, int n, int reduce_rccl) {
+  if (devices && n >= 1 && n <= NID_MAX_SHARDS) { g_host_devices = n; g_host_device0 = devices[0]; g_host_world = 1; }  // (what nid_legacy_set_devices accepts)
+  nid_legacy_set_devices(devices, n, reduce_rccl);
+}
 void nid_host_set_resident(int on) { nid_legacy_set_resident(on); }
-void nid_host_set_rank(int device, int rank, int world, const uint8_t *rccl_id128) { nid_legacy_set_rank(device, rank, world, rccl_id128); }
+void nid_host_set_rank(int device, int rank, int world, const uint8_t *rccl_id128) {
+  g_host_devices = 1; g_host_device0 = device; g_host_world = world < 1 ? 1 : world;
+  nid_legacy_set_rank(device, rank, world, rccl_id128);
+}
+void nid_host_set_launch_shape(int jac_threads, int cost_threads) {
+  g_host_jac_threads = jac_threads; g_host_cost_threads = cost_threads;
+  nid_legacy_set_launch_shape(jac_threads, cost_threads);
+}
 
 int nid_host_run_lm(const nid_pose_problem *pb, double *pose7_inout, nid_host_lm_record *trace,
                     int max_trace, char *log_buf, int log_cap) {

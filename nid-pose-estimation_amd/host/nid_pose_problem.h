@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "nid/nid_multistart.h"
+#include "nid/nid_pyr.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -76,12 +77,36 @@ int nid_host_run_pyramid_lm(const nid_pose_problem *pb, int levels, double *pose
 void nid_pyr_down_u8(const uint8_t *src, int rows, int cols, uint8_t *dst);
 void nid_pyr_down_depth_u16(const uint16_t *src, int rows, int cols, double depth_factor, uint16_t *dst);
 
+/* Coarse-to-fine MULTI-START LM on a device-built, resident pyramid (include/nid/nid_pyr.h): the pair of *pb is uploaded
+ * once, every coarser level is made on the device, and nid_pyr_multistart_lm runs n chains from poses7_in (n x 7) on the
+ * coarsest level and the best keep[l] survivors on every finer one (keep[levels], NULL: n everywhere; pose_ref7: the
+ * coarsest level's reference pose, NULL: the first start), pb->iterations outer iterations at most per level; pb->fused is
+ * ignored.  One nid_pyr is kept per process, keyed on geometry, bins and device, and rebuilt when they change
+ * (nid_host_release_pyramid drops it).  Every level context gets the options the operators give theirs for this pb:
+ * Jacobian bound and math mode from pb, the 4x4 transform, and the launch shape of nid_host_set_launch_shape (default: 512
+ * threads for the Jacobian launch up to 256 cells, 256 beyond) -- one chain takes nid_host_run_pyramid_lm's decisions.
+ * results / origin (levels x n, coarsest level first), rounds[levels] (may be NULL), *best_origin and best_pose7[7] as
+ * nid_pyr_multistart_lm gives them.  This path talks to libnid_hip.so directly, not through the operators.
+ * Returns 0, or -1 bad arguments, -2 sizes not divisible, -3 the pyramid could not be created or set up, -4 more than one
+ * device or rank is configured (nid_host_set_devices / nid_host_set_rank), -5 nid_pyr_multistart_lm failed (its message in
+ * log_buf). */
+int nid_host_run_pyramid_multistart_lm(const nid_pose_problem *pb, int levels, const double *poses7_in, int n,
+                                       const double *pose_ref7, const int32_t *keep, nid_ms_result *results, int32_t *origin,
+                                       int32_t *rounds, int *best_origin, double *best_pose7, char *log_buf, int log_cap);
+void nid_host_release_pyramid(void);
+
 /* Multi-GPU (include/nid/nid_multi.h, include/nid/legacy_ops.h): every later nid_host_run_lm /
  * nid_host_run_pyramid_lm shards the cells of each frame pair (each pyramid level) over these devices of this
  * process (entries may repeat; reduce_rccl: sum the 6x6 blocks with RCCL instead of on the host) ... */
 void nid_host_set_devices(const int32_t *devices, int n, int reduce_rccl);
 /* nid_legacy_set_resident (include/nid/legacy_ops.h) for C callers */
 void nid_host_set_resident(int on);
+/* nid_legacy_set_launch_shape (include/nid/legacy_ops.h) for callers of this layer: the operators' launches AND the level
+ * contexts of nid_host_run_pyramid_multistart_lm */
+void nid_host_set_launch_shape(int jac_threads, int cost_threads);
+/* what nid_host_set_devices / nid_host_set_rank / nid_host_set_launch_shape were last told (any pointer may be NULL):
+ * devices of this process, the first of them, ranks; jac_threads -1 = by cell count */
+void nid_host_configured(int *devices, int *device0, int *world, int *jac_threads, int *cost_threads);
 /* ... or runs as rank `rank` of `world` processes, one per GPU, summing with RCCL (id: nid_multi_comm_unique_id
  * of rank 0).  Every rank runs the same optimisation and takes the same decisions. */
 void nid_host_set_rank(int device, int rank, int world, const uint8_t *rccl_id128);

@@ -18,11 +18,14 @@
 // problem (nid_host_run_lm), i.e. the same operators and the same HIP kernels.
 #include <cstdint>
 #include <cstdio>
+#include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "nid/nid_c.h"
+#include "nid/nid_pyr.h"
 #include "nid_pose_problem.h"
 
 extern "C" {
@@ -105,6 +108,69 @@ int nid_host_run_pyramid_lm(const nid_pose_problem *pb, int levels, double *pose
   }
   if (log_buf && log_cap > 0) std::snprintf(log_buf, (size_t)log_cap, "%s", log.c_str());
   return total;
+}
+
+// ---- coarse-to-fine multi-start LM on a device-built pyramid (include/nid/nid_pyr.h) ----
+// One nid_pyr per process, keyed on geometry, bins and device; straight on libnid_hip.so (the operators' contexts and their
+// cache are not involved: the pair goes up once, here, and the levels stay on the device).
+namespace {
+struct HostPyramid {
+  nid_pyr *p = nullptr;
+  nid_config cfg{};
+  int levels = 0;
+} g_pyr;
+}  // namespace
+
+void nid_host_release_pyramid(void) {
+  if (g_pyr.p) nid_pyr_destroy(g_pyr.p);
+  g_pyr = HostPyramid();
+}
+
+int nid_host_run_pyramid_multistart_lm(const nid_pose_problem *pb, int levels, const double *poses7_in, int n,
+                                       const double *pose_ref7, const int32_t *keep, nid_ms_result *results, int32_t *origin,
+                                       int32_t *rounds, int *best_origin, double *best_pose7, char *log_buf, int log_cap) {
+  if (!pb || !poses7_in || !results || !origin || n < 1 || levels < 1 || levels > NID_PYR_MAX_LEVELS) return -1;
+  auto say = [&](const char *what, const char *detail) {
+    if (log_buf && log_cap > 0) std::snprintf(log_buf, (size_t)log_cap, "%s%s%s", what, detail[0] ? ": " : "", detail);
+  };
+  int devices = 1, device0 = 0, world = 1, jac_threads = -1, cost_threads = 0;
+  nid_host_configured(&devices, &device0, &world, &jac_threads, &cost_threads);
+  if (devices != 1 || world != 1) {
+    say("nid_host_run_pyramid_multistart_lm needs ONE device and rank: the chains are stepped on the device that evaluates them", "");
+    return -4;
+  }
+  nid_config cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  cfg.rows = pb->rows; cfg.cols = pb->cols; cfg.cell_num = pb->cell_num; cfg.bin_num = pb->bin_num; cfg.bs_degree = 3;
+  cfg.device = device0;
+  cfg.fx = pb->fx; cfg.fy = pb->fy; cfg.cx = pb->cx; cfg.cy = pb->cy;
+  nid_config coarsest;
+  if (nid_pyr_level_config(&cfg, levels - 1, &coarsest) != NID_OK) return -2;
+  if (!g_pyr.p || g_pyr.levels != levels || std::memcmp(&g_pyr.cfg, &cfg, sizeof(cfg)) != 0) {
+    nid_host_release_pyramid();
+    const int rc = nid_pyr_create(&cfg, levels, &g_pyr.p);
+    if (rc != NID_OK) { g_pyr.p = nullptr; say("nid_pyr_create", nid_status_string(rc)); return -3; }
+    g_pyr.cfg = cfg; g_pyr.levels = levels;
+  }
+  nid_pyr *p = g_pyr.p;
+  // the options the operators give their contexts for this pb (host/legacy_ops.cpp, apply_options)
+  for (int l = 0; l < levels; l++) {
+    nid_ctx *ctx = nid_pyr_level(p, l);
+    nid_config c;
+    (void)nid_pyr_level_config(&cfg, l, &c);
+    const int jt = jac_threads >= 0 ? jac_threads : (c.cell_num * c.cell_num <= 256 ? 512 : 256);
+    int rc = nid_set_options(ctx, pb->jac_bound_cuda ? NID_JACBOUND_CUDA : NID_JACBOUND_CPU, NID_XFORM_MATRIX);
+    if (rc == NID_OK) rc = nid_set_math_mode(ctx, pb->strict_math ? NID_MATH_STRICT : NID_MATH_FAST);
+    if (rc == NID_OK) rc = nid_set_launch_shape(ctx, jt, cost_threads);
+    if (rc != NID_OK) { say(nid_status_string(rc), nid_last_error(ctx)); return -3; }
+  }
+  int rc = nid_pyr_set_pair_u16(p, pb->depth_u16, pb->depth_factor, pb->im0, pb->im1, pb->T_wc0_colmajor);
+  if (rc != NID_OK) { say(nid_status_string(rc), nid_last_error(nid_pyr_level(p, 0))); return -3; }
+  const double delta = pb->huber_delta > 0 ? pb->huber_delta : std::sqrt(0.95);
+  rc = nid_pyr_multistart_lm(p, poses7_in, n, pose_ref7, pb->iterations, delta, keep, results, origin, rounds, best_origin, best_pose7);
+  if (rc != NID_OK) { say(nid_status_string(rc), nid_last_error(nid_pyr_level(p, 0))); return -5; }
+  if (log_buf && log_cap > 0) log_buf[0] = 0;
+  return 0;
 }
 
 int nid_host_standard_property(const nid_pose_problem *pb, const double *pose7, double *final_nid, char *log_buf,

@@ -211,6 +211,48 @@ def run_pyramid_lm(pair, bin_num, pose7, levels=3, iterations=10, jac_bound_cuda
     return p, per_level, log.value.decode(errors="replace")
 
 
+def run_pyramid_multistart_lm(pair, bin_num, poses7, levels=3, iterations=10, pose_ref=None, keep=None, jac_bound_cuda=False,
+                              huber_delta=None, strict=False, synth=None):
+    """Coarse-to-fine multi-start LM on a device-built pyramid (nid_host_run_pyramid_multistart_lm): n chains from poses7
+    (n x 7) on the coarsest level, the best keep[l] survivors on every finer one.  Returns (results [levels, n], origin
+    [levels, n], rounds [levels], best_origin, best_pose7) as capi.Pyramid.multistart_lm does, coarsest level first."""
+    import importlib
+    synth = synth or importlib.import_module("nid-pose-estimation_amd.synth")
+    capi = importlib.import_module("nid-pose-estimation_amd.capi")
+    pb, alive = _problem(pair, bin_num, iterations, jac_bound_cuda, 1, huber_delta, strict, synth)
+    lib = load()
+    i32p = C.POINTER(C.c_int32)
+    lib.nid_host_run_pyramid_multistart_lm.restype = C.c_int
+    lib.nid_host_run_pyramid_multistart_lm.argtypes = [C.POINTER(PoseProblem), C.c_int, c_dp, C.c_int, c_dp, i32p, C.c_void_p, i32p,
+                                                       i32p, c_ip, c_dp, C.c_char_p, C.c_int]
+    p = _d(np.asarray(poses7).reshape(-1, 7))
+    n = p.shape[0]
+    res = np.zeros((levels, max(n, 1)), dtype=capi.MS_RESULT_DTYPE)
+    origin = np.full((levels, max(n, 1)), -1, dtype=np.int32)
+    rounds = np.zeros(levels, dtype=np.int32)
+    best_pose = np.zeros(7)
+    best = C.c_int(-2)
+    ref = _d(pose_ref) if pose_ref is not None else None
+    kp = np.ascontiguousarray(keep, dtype=np.int32) if keep is not None else None
+    assert kp is None or kp.size == levels
+    log = C.create_string_buffer(4096)
+    rc = lib.nid_host_run_pyramid_multistart_lm(C.byref(pb), int(levels), _dp(p), n, _dp(ref) if ref is not None else None,
+                                                kp.ctypes.data_as(i32p) if kp is not None else None, res.ctypes.data_as(C.c_void_p),
+                                                origin.ctypes.data_as(i32p), rounds.ctypes.data_as(i32p), C.byref(best), _dp(best_pose),
+                                                log, len(log))
+    del alive
+    if rc < 0:
+        raise RuntimeError(f"nid_host_run_pyramid_multistart_lm failed ({rc}): " + log.value.decode(errors="replace"))
+    return res[:, :n], origin[:, :n], rounds, int(best.value), best_pose
+
+
+def release_pyramid():
+    """Drop the pyramid nid_host_run_pyramid_multistart_lm keeps between calls."""
+    lib = load()
+    lib.nid_host_release_pyramid.restype = None
+    lib.nid_host_release_pyramid()
+
+
 def pyr_down_u8(im):
     im = np.ascontiguousarray(im, dtype=np.uint8)
     out = np.zeros((im.shape[0] // 2, im.shape[1] // 2), dtype=np.uint8)
@@ -269,8 +311,12 @@ def set_resident(on):
 
 
 def set_launch_shape(jac_threads, cost_threads):
-    """Threads per workgroup of the legacy operators' / the host LM's launches (nid_set_launch_shape)."""
-    load().nid_legacy_set_launch_shape(int(jac_threads), int(cost_threads))
+    """Threads per workgroup of the legacy operators' / the host LM's launches (nid_set_launch_shape), and of the level
+    contexts of run_pyramid_multistart_lm."""
+    lib = load()
+    lib.nid_host_set_launch_shape.restype = None
+    lib.nid_host_set_launch_shape.argtypes = [C.c_int, C.c_int]
+    lib.nid_host_set_launch_shape(int(jac_threads), int(cost_threads))
 
 
 def set_devices(devices=(0,), reduce_rccl=False):
