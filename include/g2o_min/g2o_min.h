@@ -210,7 +210,6 @@ class BlockSolver_6_X {
   const double *b() const { return _b; }
   size_t vectorSize() const { return 6; }
   void setOptimizer(SparseOptimizer *o) { _opt = o; }
-  void setSystem(const double *H36, const double *b6) { std::memcpy(_H, H36, sizeof(_H)); std::memcpy(_b, b6, sizeof(_b)); }
  private:
   LinearSolverType *_ls;
   SparseOptimizer *_opt;
@@ -231,18 +230,24 @@ class OptimizationAlgorithmLevenberg {
   // fast path (not in the reference): take H, b, chi2 from the fused device reduction
   // (nid_normal_equations) instead of the per-edge set_h/set_j walk
   void setFusedNormalEquations(bool on) { _fused = on; }
-  // with the fused path: evaluate the whole rejection chain of an outer iteration (up to 8
-  // candidate poses) in one batched launch; decisions identical to the sequential trials
+  // with the fused path: evaluate the rejection chain of an outer iteration in slices of several candidate poses, one
+  // batched launch each, instead of pose by pose; decisions identical to the sequential trials
   void setSpeculativeTrials(bool on) { _speculative = on; }
-  // with speculative trials: evaluate the first (short) slice of the chain with its Jacobian, so that the accepted
-  // trial already carries the next iteration's H and b -- one launch per outer iteration
+  // with the fused path: evaluate the first trial of a chain with its Jacobian, so that, accepted, it already carries the
+  // next iteration's H and b -- one round trip per outer iteration
   void setSpeculativeJacobian(bool on) { _speculativeJacobian = on; }
   bool fused() const { return _fused; }
   double fusedChi() const { return _fusedChi; }
  private:
+  struct Trial {        // one candidate step of an outer iteration's chain
+    double lambda, ni;  // the damping it was solved with, and what a rejection multiplies that by
+    double x[6];        // the step; a failed solve leaves the one before it
+    bool ok;            // the LDLT succeeded
+  };
+  bool judgeTrial(const Trial &t, double trialChi, const double *b, double &currentChi, double &rho);  // :176-199, :243-250
+  SolverResult endIteration(int iteration, double iniChi, double currentChi, double rho);             // :200-224
   SolverResult solveFused(int iteration);
   double computeLambdaInit() const;                          // :227-241
-  double computeScale() const;                               // :243-250
   BlockSolver_6_X *_solver;
   SparseOptimizer *_optimizer;
   double _currentLambda, _tau, _goodStepLowerScale, _goodStepUpperScale, _ni, _lastRho;
@@ -252,6 +257,8 @@ class OptimizationAlgorithmLevenberg {
   int _speculativeFirst = 3;   // trial poses of the first slice of an outer iteration's rejection chain (see solveFused)
   int _lastTrials = 10;        // trials the previous outer iteration needed (the first iteration of a pair: all of them)
   double _fusedChi = 0.0;
+  double _chainX[6] = {0, 0, 0, 0, 0, 0};  // the step a fused chain starts from (see solveFused)
+  // the accepted first trial of an outer iteration, evaluated with its Jacobian: the next iteration's evaluation
   bool _speculativeJacobian = false, _haveNext = false;
   double _nextPose[7], _nextH[36], _nextB[6], _nextChi = 0.0;
 };
@@ -315,6 +322,7 @@ class SparseOptimizer {
  private:
   friend class OptimizationAlgorithmLevenberg;
   friend class BlockSolver_6_X;
+  void recordIteration(int iteration, double chi2);           // the verbose line and its IterationRecord, :434-440
   OptimizationAlgorithmLevenberg *_algorithm;
   std::vector<VertexSE3Expmap *> _vertices;
   std::vector<EdgeSE3ProjectIntensityOnlyPoseNID *> _edges, _activeEdges;

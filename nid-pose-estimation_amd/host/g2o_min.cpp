@@ -325,16 +325,54 @@ double OptimizationAlgorithmLevenberg::computeLambdaInit() const {
   return _tau * maxDiagonal;
 }
 
-double OptimizationAlgorithmLevenberg::computeScale() const {
-  double scale = 0.;
-  for (size_t j = 0; j < _solver->vectorSize(); j++)
-    scale += _solver->x()[j] * (_currentLambda * _solver->x()[j] + _solver->b()[j]);
-  return scale;
+// The verdict on one trial (:176-199), for every flow: rho from the trial's chi2 and its step, then either the accepted
+// step's chi2 and a lambda scaled down, or lambda scaled up.  A step whose solve failed counts as chi2 = DBL_MAX (:175).
+bool OptimizationAlgorithmLevenberg::judgeTrial(const Trial &t, double trialChi, const double *b, double &currentChi, double &rho) {
+  const double tempChi = t.ok ? trialChi : std::numeric_limits<double>::max();
+  rho = (currentChi - tempChi);
+  double scale = 0.;  // computeScale(), :243-250
+  for (int j = 0; j < 6; j++) scale += t.x[j] * (t.lambda * t.x[j] + b[j]);
+  scale += 1e-3;
+  rho /= scale;
+  if (rho > 0 && std::isfinite(tempChi)) {
+    double alpha = 1. - std::pow((2 * rho - 1), 3);
+    alpha = (std::min)(alpha, _goodStepUpperScale);
+    const double scaleFactor = (std::max)(_goodStepLowerScale, alpha);
+    _currentLambda = t.lambda * scaleFactor;
+    _ni = 2;
+    currentChi = tempChi;
+    return true;
+  }
+  _currentLambda = t.lambda * t.ni;
+  _ni = t.ni * 2;
+  return false;
 }
 
-// Fused fast path (not in the reference): H, b and the robust chi2 come straight from the device
-// reduction (nid_normal_equations) -- one kernel and 256 B per evaluation instead of the per-cell
-// arrays and the per-edge set_h/set_j walk.  Same LM control flow as solve() below.
+// The end of an outer iteration (:200-224), for every flow, after _levenbergIterations trials.
+OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::endIteration(int iteration, double iniChi, double currentChi,
+                                                                                         double rho) {
+  _lastRho = rho;
+  _fusedChi = currentChi;
+  _lastTrials = iteration == 0 ? 0 : _levenbergIterations;  // the first iteration's count says nothing about the next one's
+  if (_levenbergIterations == _maxTrialsAfterFailure || rho == 0) return Terminate;
+  if ((iniChi - currentChi) * 1e3 < iniChi) _nBad++; else _nBad = 0;
+  if (_nBad >= 3) return Terminate;
+  return OK;
+}
+
+// Fused flows (not in the reference): H, b and the robust chi2 come straight from the device reduction
+// (nid_normal_equations) -- one kernel and 256 B per evaluation instead of the per-cell arrays and the per-edge
+// set_h/set_j walk.  Same LM as solve() below, as ONE trial chain evaluated in slices:
+// the chain of an outer iteration is known in advance IF every trial is rejected -- lambda_{k+1} = lambda_k * ni_k,
+// ni_{k+1} = 2 ni_k (:196-197) -- so the next trials of a slice are solved on the host (6x6, microseconds), their poses
+// evaluated, and the verdicts read off in order until one is accepted.  Two slice policies, same poses, same chi2
+// bits, same decisions, only the launches differ:
+//  * sequential (fused 1, 4): slices of ONE pose through nid_multi_normal_equations, the single-pose evaluation the
+//    resident evaluator answers;
+//  * speculative (fused 2, 3): slices of several poses in one batched launch each (nid_multi_launch_chain).
+// With _speculativeJacobian (fused 3, 4) the FIRST trial of a chain -- the one a steady iteration accepts -- is evaluated
+// WITH the Jacobian phase: accepted, it is the next outer iteration's evaluation, one round trip per outer iteration
+// instead of two (the chi2 of a pose is the same bits with and without the Jacobian phase).
 OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::solveFused(int iteration) {
   SparseOptimizer *opt = _optimizer;
   VertexSE3Expmap *vm = opt->_vertices[0];
@@ -376,164 +414,90 @@ OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::sol
   const double t_jac = us_since(t_start);
   std::memcpy(vm->H, H, sizeof(H));
   std::memcpy(vm->b, b, sizeof(b));
-  _solver->setSystem(H, b);
-  double tempChi = currentChi;
   const double iniChi = currentChi;
   if (iteration == 0) { _currentLambda = computeLambdaInit(); _ni = 2; _nBad = 0; }
   double rho = 0;
   int &qmax = _levenbergIterations;
   qmax = 0;
-  if (_speculative) {
-    // The trial chain of one outer iteration is known in advance IF every trial is rejected:
-    // lambda_{k+1} = lambda_k * ni_k, ni_{k+1} = 2 ni_k (:196-197).  Solve all of them on the host
-    // (6x6, microseconds), evaluate the candidate poses in ONE batched cost-only launch, then replay
-    // the reference's accept/reject scan over the results.  Same poses, same chi2 bits, same
-    // decisions as the sequential loop below -- only the number of launches changes.
-    const SE3Quat T0 = vm->estimate();
-    constexpr int kTrialBatch = 16;  // one launch whose per-pose records travel as kernel arguments
-    double xprev[6], xlast[6] = {0, 0, 0, 0, 0, 0};
-    bool first_slice = true, first_of_chain = true;
-    // How many of them to evaluate at once: a steady iteration accepts its first or second trial, the first
-    // iteration of a pair needs up to seven (lambda_0 = 1e-5 max diag is far too small for this cost).  A launch of
-    // 3 trial poses costs ~15 us, one of 10 ~35 us (tools/latency_sweep.py), so the chain is evaluated in slices:
-    // as many trials as the PREVIOUS outer iteration needed (at least _speculativeFirst), then the rest.
-    // The first iteration's own count says nothing about the next one (lambda has been tuned by then).
-    int slice = iteration == 0 ? _maxTrialsAfterFailure
+
+  const SE3Quat T0 = vm->estimate();
+  constexpr int kTrialBatch = 16;  // one launch whose per-pose records travel as kernel arguments
+  // How many trials to evaluate at once when speculating: a steady iteration accepts its first or second trial, the first
+  // iteration of a pair needs up to seven (lambda_0 = 1e-5 max diag is far too small for this cost).  A launch of
+  // 3 trial poses costs ~15 us, one of 10 ~35 us (tools/latency_sweep.py), so: as many trials as the PREVIOUS outer
+  // iteration needed (at least _speculativeFirst), then, in a second slice, everything that is left.
+  int slice = !_speculative ? 1
+              : iteration == 0 ? _maxTrialsAfterFailure
                                : std::max(_speculativeFirst, std::min(_lastTrials, _maxTrialsAfterFailure));
-    while (qmax < _maxTrialsAfterFailure) {
-      const int nb = std::min(std::min(kTrialBatch, slice), _maxTrialsAfterFailure - qmax);
-      slice = kTrialBatch;  // a second slice takes everything that is left
-      double lam[kTrialBatch], nis[kTrialBatch], xs[kTrialBatch][6], poses[kTrialBatch * 7];
-      bool oks[kTrialBatch];
-      SE3Quat cand[kTrialBatch];
-      double l = _currentLambda, n_i = _ni;
-      for (int j = 0; j < 6; j++) xprev[j] = first_slice ? _solver->x()[j] : xlast[j];
-      first_slice = false;
-      for (int k = 0; k < nb; k++) {
-        lam[k] = l; nis[k] = n_i;
-        double Hl[36];
-        std::memcpy(Hl, H, sizeof(Hl));
-        for (int j = 0; j < 6; j++) Hl[j * 6 + j] += l;
-        LinearSolverDense ls;
-        for (int j = 0; j < 6; j++) xs[k][j] = (k ? xs[k - 1][j] : xprev[j]);  // failed solve leaves x untouched
-        oks[k] = ls.solve(Hl, xs[k], b);
-        Vector6d u;
-        for (int j = 0; j < 6; j++) u[j] = xs[k][j];
-        cand[k] = SE3Quat::exp(u) * T0;
-        cand[k].toPose7(poses + 7 * k);
-        l *= n_i; n_i *= 2;
-      }
-      const auto t_slice = std::chrono::steady_clock::now();
-      const double t_prep = us_since(t_start);
-      // The FIRST trial of the chain -- the one a steady iteration accepts -- is evaluated WITH the Jacobian phase,
-      // concurrently with the cost-only launch of the others (nid_launch_chain): if it is accepted, the next outer
-      // iteration's H and b are already on the host -- one round trip per outer iteration instead of two (the chi2
-      // of a pose is the same bits with and without the Jacobian phase).
-      const int n_jac = (_speculativeJacobian && first_of_chain) ? 1 : 0;
-      first_of_chain = false;
+  // A failed solve leaves x as it was, so its trial repeats the step before it; the FIRST step of a chain has none:
+  // the sequential policy then repeats the last step of the chain before (what the reference's solver object holds),
+  // the speculative policy a zero step.
+  double x[6];
+  std::memcpy(x, _chainX, sizeof(x));
+  bool accepted = false;
+  while (qmax < _maxTrialsAfterFailure) {
+    const int nb = std::min(std::min(kTrialBatch, slice), _maxTrialsAfterFailure - qmax);
+    if (_speculative) slice = kTrialBatch;
+    Trial trial[kTrialBatch];
+    SE3Quat cand[kTrialBatch];
+    double poses[kTrialBatch * 7], chis[kTrialBatch], H0[36], b0[6];
+    double l = _currentLambda, n_i = _ni;
+    for (int k = 0; k < nb; k++) {
+      Trial &t = trial[k];
+      t.lambda = l; t.ni = n_i;
+      double Hl[36];
+      std::memcpy(Hl, H, sizeof(Hl));
+      for (int j = 0; j < 6; j++) Hl[j * 6 + j] += l;
+      t.ok = LinearSolverDense().solve(Hl, x, b);
+      Vector6d u;
+      for (int j = 0; j < 6; j++) t.x[j] = u[j] = x[j];
+      cand[k] = SE3Quat::exp(u) * T0;
+      cand[k].toPose7(poses + 7 * k);
+      l *= n_i; n_i *= 2;
+    }
+    const auto t_slice = std::chrono::steady_clock::now();
+    const double t_prep = lm_trace ? us_since(t_start) : 0.0;
+    const int n_jac = (_speculativeJacobian && qmax == 0) ? 1 : 0;  // the first trial of the chain
+    if (_speculative) {
       if (nid_multi_launch_chain(ctx, 0, nb, poses, n_jac, delta) != NID_OK) return Fail;
-      double chis[kTrialBatch], H0[36], b0[6];
       for (int k = 0; k < nb; k++)
         if (nid_multi_wait(ctx, k, k < n_jac ? H0 : nullptr, k < n_jac ? b0 : nullptr, &chis[k], &na) != NID_OK) return Fail;
       if (lm_trace)
         std::fprintf(stderr, "[lm] it %d: setup until %.1f us, J until %.1f us, host solves until %.1f us, %d trial poses%s %.1f us\n", iteration,
                      t_setup, t_jac, t_prep, nb, n_jac ? " (first with J)" : "", us_since(t_slice));
-      bool accepted = false;
-      for (int k = 0; k < nb; k++) {
-        tempChi = oks[k] ? chis[k] : std::numeric_limits<double>::max();
-        rho = (currentChi - tempChi);
-        double scale = 0.;
-        for (int j = 0; j < 6; j++) scale += xs[k][j] * (lam[k] * xs[k][j] + b[j]);
-        scale += 1e-3;
-        rho /= scale;
-        qmax++;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = (std::min)(alpha, _goodStepUpperScale);
-          const double scaleFactor = (std::max)(_goodStepLowerScale, alpha);
-          _currentLambda = lam[k] * scaleFactor;
-          _ni = 2;
-          currentChi = tempChi;
-          vm->setEstimate(cand[k]);
-          accepted = true;
-          if (k < n_jac) {
-            _haveNext = true;
-            std::memcpy(_nextPose, poses + 7 * k, sizeof(_nextPose));
-            std::memcpy(_nextH, H0, sizeof(_nextH));
-            std::memcpy(_nextB, b0, sizeof(_nextB));
-            _nextChi = chis[k];
-          }
-          break;
-        }
-        _currentLambda = lam[k] * nis[k];
-        _ni = nis[k] * 2;
-        if (!(rho < 0)) break;  // rho == 0 (or NaN): the reference's do/while stops here
-      }
-      for (int j = 0; j < 6; j++) xlast[j] = xs[nb - 1][j];
-      if (accepted || !(rho < 0)) break;
-    }
-    _lastRho = rho;
-    _fusedChi = currentChi;
-    _lastTrials = iteration == 0 ? 0 : qmax;
-    if (qmax == _maxTrialsAfterFailure || rho == 0) return Terminate;
-    if ((iniChi - currentChi) * 1e3 < iniChi) _nBad++; else _nBad = 0;
-    if (_nBad >= 3) return Terminate;
-    return OK;
-  }
-  do {
-    opt->push();
-    _solver->setLambda(_currentLambda, true);
-    const bool ok2 = _solver->solve();
-    opt->update(_solver->x());
-    _solver->restoreDiagonal();
-    opt->_vertices[0]->estimate().toPose7(p7);
-    // The FIRST trial -- the one a steady iteration accepts -- is evaluated WITH its Jacobian if asked for
-    // (setSpeculativeJacobian without speculative trials: fused 4): accepted, it IS the next outer iteration's
-    // evaluation -- one single-pose round trip per outer iteration, which is what the resident evaluator answers
-    // fastest (the chi2 of a pose is the same bits with and without the Jacobian phase).
-    const bool with_jac = _speculativeJacobian && qmax == 0;
-    double H0[36], b0[6];
-    if (nid_multi_normal_equations(ctx, p7, with_jac ? 1 : 0, delta, with_jac ? H0 : nullptr, with_jac ? b0 : nullptr, &tempChi, &na) != NID_OK)
+    } else if (nid_multi_normal_equations(ctx, poses, n_jac, delta, n_jac ? H0 : nullptr, n_jac ? b0 : nullptr, &chis[0], &na) != NID_OK) {
+      vm->setEstimate(cand[0]);  // like the reference's loop, which has moved the vertex to the trial when its evaluation fails
       return Fail;
-    const double trialChi = tempChi;
-    if (!ok2) tempChi = std::numeric_limits<double>::max();
-    rho = (currentChi - tempChi);
-    double scale = computeScale();
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0 && std::isfinite(tempChi)) {
-      double alpha = 1. - std::pow((2 * rho - 1), 3);
-      alpha = (std::min)(alpha, _goodStepUpperScale);
-      const double scaleFactor = (std::max)(_goodStepLowerScale, alpha);
-      _currentLambda *= scaleFactor;
-      _ni = 2;
-      currentChi = tempChi;
-      opt->discardTop();
-      if (with_jac) {
-        _haveNext = true;
-        std::memcpy(_nextPose, p7, sizeof(_nextPose));
-        std::memcpy(_nextH, H0, sizeof(_nextH));
-        std::memcpy(_nextB, b0, sizeof(_nextB));
-        _nextChi = trialChi;
-      }
-    } else {
-      _currentLambda *= _ni;
-      _ni *= 2;
-      opt->pop();
     }
-    qmax++;
-  } while (rho < 0 && qmax < _maxTrialsAfterFailure);
-  if (lm_trace)
-    std::fprintf(stderr, "[lm] it %d: setup until %.1f us, J until %.1f us%s, %d sequential trials%s, end %.1f us\n", iteration, t_setup, t_jac,
-                 t_jac - t_setup < 2.0 ? " (carried over)" : "", qmax, _speculativeJacobian ? " (first with J)" : "", us_since(t_start));
-  _lastRho = rho;
-  _fusedChi = currentChi;
-  if (qmax == _maxTrialsAfterFailure || rho == 0) return Terminate;
-  if ((iniChi - currentChi) * 1e3 < iniChi) _nBad++; else _nBad = 0;
-  if (_nBad >= 3) return Terminate;
-  return OK;
+    for (int k = 0; k < nb && !accepted; k++) {
+      accepted = judgeTrial(trial[k], chis[k], b, currentChi, rho);
+      qmax++;
+      if (accepted) {
+        vm->setEstimate(cand[k]);
+        if (k < n_jac) {
+          _haveNext = true;
+          std::memcpy(_nextPose, poses + 7 * k, sizeof(_nextPose));
+          std::memcpy(_nextH, H0, sizeof(_nextH));
+          std::memcpy(_nextB, b0, sizeof(_nextB));
+          _nextChi = chis[k];
+        }
+      } else if (!(rho < 0)) {
+        break;  // rho == 0 (or NaN): the reference's do/while stops here
+      }
+    }
+    if (accepted || !(rho < 0)) break;
+  }
+  if (!_speculative) {
+    std::memcpy(_chainX, x, sizeof(_chainX));
+    if (lm_trace)
+      std::fprintf(stderr, "[lm] it %d: setup until %.1f us, J until %.1f us%s, %d sequential trials%s, end %.1f us\n", iteration, t_setup, t_jac,
+                   t_jac - t_setup < 2.0 ? " (carried over)" : "", qmax, _speculativeJacobian ? " (first with J)" : "", us_since(t_start));
+  }
+  return endIteration(iteration, iniChi, currentChi, rho);
 }
 
+// The per-edge flow: the reference's loop and its call schedule on the operators -- CudaComputeH with the Jacobian (:98),
+// buildSystem, one cost-only CudaComputeH per trial (:173) -- with the verdicts and the end of the iteration above.
 OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::solve(int iteration) {
   if (_fused) return solveFused(iteration);
   SparseOptimizer *opt = _optimizer;
@@ -549,7 +513,6 @@ OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::sol
   opt->set_h_pointer(Htarget.data(), Hjoint.data());
   if (!opt->computeActiveErrors()) return Fail;
   double currentChi = opt->activeRobustChi2();
-  double tempChi = currentChi;
   const double iniChi = currentChi;
   _solver->set_j_bs(der.data());
   if (!_solver->buildSystem()) return Fail;
@@ -564,8 +527,11 @@ OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::sol
   qmax = 0;
   do {
     opt->push();
+    Trial t;
+    t.lambda = _currentLambda; t.ni = _ni;
     _solver->setLambda(_currentLambda, true);
-    const bool ok2 = _solver->solve();
+    t.ok = _solver->solve();
+    std::memcpy(t.x, _solver->x(), sizeof(t.x));
     opt->update(_solver->x());
     VertexSE3Expmap *vn = opt->_vertices[0];
     _solver->restoreDiagonal();
@@ -578,35 +544,11 @@ OptimizationAlgorithmLevenberg::SolverResult OptimizationAlgorithmLevenberg::sol
                  opt->cell_num_, opt->rows_, opt->cols_, opt->Href_, nullptr, nullptr, Htarget.data(),
                  Hjoint.data(), der.data());
     if (!opt->computeActiveErrors()) return Fail;
-    tempChi = opt->activeRobustChi2();
-    if (!ok2) tempChi = std::numeric_limits<double>::max();
-
-    rho = (currentChi - tempChi);
-    double scale = computeScale();
-    scale += 1e-3;
-    rho /= scale;
-
-    if (rho > 0 && std::isfinite(tempChi)) {
-      double alpha = 1. - std::pow((2 * rho - 1), 3);
-      alpha = (std::min)(alpha, _goodStepUpperScale);
-      const double scaleFactor = (std::max)(_goodStepLowerScale, alpha);
-      _currentLambda *= scaleFactor;
-      _ni = 2;
-      currentChi = tempChi;
-      opt->discardTop();
-    } else {
-      _currentLambda *= _ni;
-      _ni *= 2;
-      opt->pop();
-    }
+    if (judgeTrial(t, opt->activeRobustChi2(), _solver->b(), currentChi, rho)) opt->discardTop();
+    else opt->pop();
     qmax++;
   } while (rho < 0 && qmax < _maxTrialsAfterFailure);
-  _lastRho = rho;
-
-  if (qmax == _maxTrialsAfterFailure || rho == 0) return Terminate;
-  if ((iniChi - currentChi) * 1e3 < iniChi) _nBad++; else _nBad = 0;
-  if (_nBad >= 3) return Terminate;
-  return OK;
+  return endIteration(iteration, iniChi, currentChi, rho);
 }
 
 // ---------------------------------------------------------------------------- optimizer
@@ -670,6 +612,20 @@ void SparseOptimizer::push() { _vertices[0]->push(); }
 void SparseOptimizer::pop() { _vertices[0]->pop(); }
 void SparseOptimizer::discardTop() { _vertices[0]->discardTop(); }
 
+void SparseOptimizer::recordIteration(int iteration, double chi2) {  // sparse_optimizer.cpp:434-440
+  if (_log) {
+    char buf[256];
+    std::snprintf(buf, sizeof(buf), "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6f\t levenbergIter= %d\n",
+                  iteration, chi2, (int)_activeEdges.size(), _algorithm->currentLambda(), _algorithm->levenbergIteration());
+    (*_log) << buf;
+  }
+  IterationRecord r;
+  r.iteration = iteration; r.chi2 = chi2; r.lambda = _algorithm->currentLambda(); r.rho = _algorithm->lastRho();
+  r.levenbergIter = _algorithm->levenbergIteration();
+  _vertices[0]->estimate().toPose7(r.pose7);
+  _trace.push_back(r);
+}
+
 int SparseOptimizer::optimize(int iterations) {  // sparse_optimizer.cpp:356-450
   if (_vertices.empty() || !_algorithm) {
     std::cerr << "SparseOptimizer::optimize: 0 vertices to optimize, maybe forgot to call initializeOptimization()\n";
@@ -704,51 +660,27 @@ int SparseOptimizer::optimize(int iterations) {  // sparse_optimizer.cpp:356-450
     } stat_scope{this, i, t_it0};
     result = _algorithm->solve(i);
     ok = (result == OptimizationAlgorithmLevenberg::OK);
-    if (verbose() && _algorithm->fused()) {
-      // fused mode: the accepted pose's robust chi2 is already known; skip the extra evaluation
-      const double chi = _algorithm->fusedChi();
-      if (_log) {
-        char buf[256];
-        std::snprintf(buf, sizeof(buf), "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6f\t levenbergIter= %d\n",
-                      i, chi, (int)_activeEdges.size(), _algorithm->currentLambda(), _algorithm->levenbergIteration());
-        (*_log) << buf;
-      }
-      IterationRecord r;
-      r.iteration = i; r.chi2 = chi; r.lambda = _algorithm->currentLambda(); r.rho = _algorithm->lastRho();
-      r.levenbergIter = _algorithm->levenbergIteration();
-      _vertices[0]->estimate().toPose7(r.pose7);
-      _trace.push_back(r);
-      robustchi2_his_[i] = chi;
-      ++cjIterations;
-      continue;
-    }
+    const bool chi_known = verbose() && _algorithm->fused();  // fused: the accepted pose's robust chi2 is already known
     if (verbose()) {
-      // the verbose branch evaluates the cost once more at the accepted pose (:404-427)
-      const int n2 = cell_num_ * cell_num_;
-      std::vector<double> Htarget(n2, 0.0), Hjoint(n2, 0.0);
-      Matrix4d M = _vertices[0]->estimate().to_homogeneous_matrix();
-      CudaComputeH(false, im0_, im1_, points3d_, bs_counter_, bs_value_ref_, bs_index_ref_, M.data(),
-                   camera_intrincis_, bin_num_, bs_degree_, cell_num_, rows_, cols_, Href_, nullptr, nullptr,
-                   Htarget.data(), Hjoint.data(), nullptr);
-      set_h_pointer(Htarget.data(), Hjoint.data());
-      const bool walked = computeActiveErrors();
-      set_h_pointer(nullptr, nullptr);
-      if (!walked) return 0;
-      const double chi = activeRobustChi2();
-      if (_log) {
-        char buf[256];
-        std::snprintf(buf, sizeof(buf), "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6f\t levenbergIter= %d\n",
-                      i, chi, (int)_activeEdges.size(), _algorithm->currentLambda(), _algorithm->levenbergIteration());
-        (*_log) << buf;
+      double chi = _algorithm->fusedChi();
+      if (!chi_known) {
+        // the verbose branch evaluates the cost once more at the accepted pose (:404-427)
+        const int n2 = cell_num_ * cell_num_;
+        std::vector<double> Htarget(n2, 0.0), Hjoint(n2, 0.0);
+        Matrix4d M = _vertices[0]->estimate().to_homogeneous_matrix();
+        CudaComputeH(false, im0_, im1_, points3d_, bs_counter_, bs_value_ref_, bs_index_ref_, M.data(),
+                     camera_intrincis_, bin_num_, bs_degree_, cell_num_, rows_, cols_, Href_, nullptr, nullptr,
+                     Htarget.data(), Hjoint.data(), nullptr);
+        set_h_pointer(Htarget.data(), Hjoint.data());
+        const bool walked = computeActiveErrors();
+        set_h_pointer(nullptr, nullptr);
+        if (!walked) return 0;
+        chi = activeRobustChi2();
       }
-      IterationRecord r;
-      r.iteration = i; r.chi2 = chi; r.lambda = _algorithm->currentLambda(); r.rho = _algorithm->lastRho();
-      r.levenbergIter = _algorithm->levenbergIteration();
-      _vertices[0]->estimate().toPose7(r.pose7);
-      _trace.push_back(r);
+      recordIteration(i, chi);
     }
     ++cjIterations;
-    robustchi2_his_[i] = activeRobustChi2();
+    robustchi2_his_[i] = chi_known ? _algorithm->fusedChi() : activeRobustChi2();
   }
   if (result == OptimizationAlgorithmLevenberg::Fail) return 0;
   return cjIterations;
