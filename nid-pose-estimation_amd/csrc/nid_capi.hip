@@ -25,6 +25,7 @@
 #include "nid/nid_pyr.h"
 #include "nid_eval_launch.h"
 #include "nid_pose_pool.h"             // pose_sizes, seq_fusion: per-pose buffer sizes and the fused grids' budget rule (no HIP in it)
+#include "nid_direct_sum.h"            // DirectSum, add_block: the host's arithmetic and order of a DIRECT / GROUP-DIRECT launch (no HIP in it)
 #include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
 #include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_pyr_down, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
@@ -32,6 +33,20 @@
 using namespace nid;
 
 namespace {
+
+// How the result of the launch in flight in a slot comes home: ONE route per launch, set where the launch is made
+// (launch_slot, launch_batch, evaluate_common), changed only by resident_fallback (a resident request re-issued as a
+// launch), resident_served and resident_quiesce (a request collected early), and read by nid_wait's switch.
+enum class Delivery : unsigned char {
+  SeqWord,          // in-launch reduction into reduced_host; the last workgroup posts the sequence word (wait_host_seq)
+  Direct,           // DIRECT: per-cell records into quad_host, the host forms and sums the quadratic forms (wait_direct)
+  Groups,           // GROUP-DIRECT (nid_set_direct_results(ctx, 2)): group sums into groups_host (wait_groups)
+  Cellout,          // the blocking per-cell calls: the cells' outputs into cellout_host, word by word (wait_direct_cellout)
+  ResidentRecords,  // a request to the resident kernel; its records arrive in ctx->res.rec_host (wait_direct)
+  ResidentCellout,  // ... its per-cell outputs in cellout_host (wait_direct_cellout)
+  Event,            // a caller-owned result buffer: over when slot done_slot's `done` event is
+  Collected,        // the result is in reduced_host already (resident_quiesce): nid_wait only hands it over
+};
 
 struct Slot {
   double *cellout_dev = nullptr;
@@ -44,21 +59,19 @@ struct Slot {
   double *quad_host_devptr = nullptr;
   double *groups_host = nullptr;   // pinned, mapped, created on first use: [ngroups][32] group sums of a GROUP-DIRECT launch (wait_groups)
   double *groups_host_devptr = nullptr;
-  bool groups = false;             // the launch in flight is a GROUP-DIRECT one (nid_set_direct_results(ctx, 2))
-  bool groups_dirty = false;
-  bool direct = false;             // the launch in flight is a DIRECT one: the host forms and sums the cells' quadratic forms
-  bool resident = false;           // ... it is a request to the resident kernel (its records arrive in ctx->res.rec_host)
-  bool collected = false;          // its result is in reduced_host already (resident_quiesce): nid_wait only hands it over
-  bool quad_dirty = false;         // a DIRECT launch wrote (or may still write) into quad_host and wait_direct has not consumed it
-  bool direct_jac = false;         // ... it carries Jacobians
+  Delivery delivery = Delivery::SeqWord;  // the route home of the launch in flight (meaningful while `pending`, and inside a blocking call)
+  // properties of the BUFFERS, whatever the route: a launch wrote (or may still write) into quad_host / groups_host and
+  // no wait has consumed it
+  bool quad_dirty = false, groups_dirty = false;
+  bool direct_jac = false;         // the DIRECT launch or resident request in flight carries Jacobians
   double direct_delta = 0.0;       // ... its Huber delta
   unsigned long long seq = 0;      // sequence number of the last launch into this slot
   hipEvent_t done = nullptr, e0 = nullptr, e1 = nullptr;  // e0 / e1: timing events, created on first use
   bool pending = false;
   bool timed = false;
-  bool external_target = false;
-  int done_slot = 0;               // external targets: the slot whose `done` event covers this one's launch
+  int done_slot = 0;               // Delivery::Event: the slot whose `done` event covers this one's launch
 };
+inline bool is_resident(const Slot &S) { return S.delivery == Delivery::ResidentRecords || S.delivery == Delivery::ResidentCellout; }
 
 // What every pose of a grid needs for itself: per-cell blocks, group sums, tickets (zero between launches: the kernels
 // leave them so) and -- for a private grid -- its argument record (pinned mirror + device array).  The public slots are
@@ -72,6 +85,7 @@ struct PosePool {
 };
 static_assert(sizeof(SlotArgs) == 224, "the budget rule's table (tests/cpp/pose_pool_check.cpp) assumes this record");
 static_assert(kPoseBlock == kQuad && kPoseBlock == kReducedLen && kSeqGridLimit == kSeqGridMax, "nid_pose_pool.h restates these");
+static_assert(kSumBlock == kQuad && kSumBlock == kReducedLen, "nid_direct_sum.h restates these");
 
 }  // namespace
 
@@ -485,39 +499,34 @@ int refuse_pending(nid_ctx *ctx) {
 
 // ---- DIRECT launches ---------------------------------------------------------------------------------------------
 // One pose, the host is waiting for the result (a Gauss-Newton / LM loop is a chain of such launches).  Every cell's
-// workgroup writes its record -- err, J[6], an active flag: 64 bytes -- straight to pinned host memory and the HOST
-// forms the Huber-weighted quadratic forms (RobustKernelHuber::robustify robust_kernel_impl.cpp:77-91 with the float
-// dsqr, constructQuadraticForm base_unary_edge.hpp:56-63: the kernel's operations in the kernel's order, all IEEE) and
-// adds them up in the order the in-launch reduction uses (sum_blocks_w0 twice: per group the even-numbered cells in
-// ascending order plus the odd-numbered ones, then the groups likewise), so the 6x6 system has the same bits either
-// way.  The launch has no ticket, no device-scope round trip and no fence; for the host it is over when the last
-// cell's 64 bytes have crossed PCIe.  No word is ordered against any other: the host pre-fills the records with a
-// sentinel no arithmetic produces and polls every word; a consumed record is reset on the spot.  (Round 2 measured 5 us
+// workgroup writes its record straight to pinned host memory and the HOST forms the Huber-weighted quadratic forms and
+// adds them up in the in-launch reduction's order: the arithmetic, the order and the sentinel protocol are
+// nid_direct_sum.h's (no HIP in it; tests/cpp/direct_sum_check.cpp).  The launch has no ticket, no device-scope round
+// trip and no fence; for the host it is over when the last cell's 64 bytes have crossed PCIe.  (Round 2 measured 5 us
 // of reduction tail behind the last workgroup of a single-pose launch: seven dependent device-scope round trips; a
 // first version of this path that shipped the cells' finished 32-double blocks spent 4.5 us reading 64 KB of freshly
 // written host memory behind the last arrival.)
-void fill_sentinel(double *p, size_t n) {
-  unsigned long long *q = reinterpret_cast<unsigned long long *>(p);
-  for (size_t i = 0; i < n; i++) q[i] = kHostSentinel;
-}
 
-int ensure_quad_host(nid_ctx *ctx, Slot &S) {
-  if (S.quad_host && S.quad_dirty) {
-    // the previous DIRECT launch into this buffer was never collected (its wait failed): let it finish, start clean
+// A pinned, mapped buffer of n sentinel-filled words for a launch's results, made on first use.  dirty: the previous
+// launch into it was never collected (its wait failed): let it finish, start clean
+int ensure_host_words(nid_ctx *ctx, double *&host, double *&devptr, bool &dirty, size_t n) {
+  if (host && dirty) {
     NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
     NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-    fill_sentinel(S.quad_host, (size_t)2 * ctx->g.nloc * kDirectRec);
-    S.quad_dirty = false;
+    fill_sentinel(host, n);
+    dirty = false;
   }
-  if (S.quad_host) return NID_OK;
-  const size_t n = (size_t)2 * ctx->g.nloc * kDirectRec;
-  if (hipHostMalloc(reinterpret_cast<void **>(&S.quad_host), n * sizeof(double), hipHostMallocMapped) != hipSuccess) {
-    S.quad_host = nullptr;
+  if (host) return NID_OK;
+  if (hipHostMalloc(reinterpret_cast<void **>(&host), n * sizeof(double), hipHostMallocMapped) != hipSuccess) {
+    host = nullptr;
     return NID_ERR_NOMEM;
   }
-  fill_sentinel(S.quad_host, n);
-  NID_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&S.quad_host_devptr), S.quad_host, 0));
+  fill_sentinel(host, n);
+  NID_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&devptr), host, 0));
   return NID_OK;
+}
+int ensure_quad_host(nid_ctx *ctx, Slot &S) {
+  return ensure_host_words(ctx, S.quad_host, S.quad_host_devptr, S.quad_dirty, (size_t)2 * ctx->g.nloc * kDirectRec);
 }
 
 // may this launch be DIRECT?  (timed and diagnostic launches keep the in-launch reduction: they may be re-issued into
@@ -526,220 +535,100 @@ bool direct_ok(const nid_ctx *ctx) {
   return ctx->direct_results && !ctx->timing && !ctx->dbg_enabled && !ctx->dbg_stamps;
 }
 
-// GROUP-DIRECT (nid_set_direct_results(ctx, 2)): the whole per-cell tail stays on the device -- Huber kernel, quadratic
-// form, and the first level of the reduction (every group's last workgroup sums its group's blocks) -- and the group
-// sums go straight to pinned host memory, one 256-byte block per group; the host adds the <= 32 group blocks in
-// sum_blocks_w0's order (the second level: even-numbered groups ascending plus the odd-numbered ones).  Against the
-// in-launch reduction it saves the second ticket round trip, the re-read of the group sums and the system-scope fence;
-// against DIRECT it keeps a15 on the GPU and costs the first ticket round trip.  Same bits as both.
-int ensure_groups_host(nid_ctx *ctx, Slot &S) {
-  const int ngroups = (ctx->g.nloc + ctx->group_size - 1) / ctx->group_size;
-  const size_t n = (size_t)ngroups * kQuad;
-  if (S.groups_host && S.groups_dirty) {
-    NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-    fill_sentinel(S.groups_host, n);
-    S.groups_dirty = false;
-  }
-  if (S.groups_host) return NID_OK;
-  if (hipHostMalloc(reinterpret_cast<void **>(&S.groups_host), n * sizeof(double), hipHostMallocMapped) != hipSuccess) {
-    S.groups_host = nullptr;
-    return NID_ERR_NOMEM;
-  }
-  fill_sentinel(S.groups_host, n);
-  NID_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&S.groups_host_devptr), S.groups_host, 0));
-  return NID_OK;
-}
-
-// true when all `n` words at p have arrived
-inline bool words_arrived(const double *p, int n) {
-  const volatile unsigned long long *q = reinterpret_cast<const volatile unsigned long long *>(p);
-  for (int i = 0; i < n; i++)
-    if (q[i] == kHostSentinel) return false;
-  return true;
-}
-
 // NID_DIRECT_TRACE=1 (experiments): per wait, microseconds from entering wait_direct to the first cell's arrival, to
 // the last moment the host had to WAIT for a cell, and to the end (the difference of the last two = the host's own
 // backlog behind the last arrival); averages printed every 2000 waits
 struct DirectTrace { double first = 0, last_wait = 0, end = 0; long n = 0; };
 static DirectTrace g_dtrace;
 
-// spin until `arrived()`; after a long while let a device error surface through the runtime, then give up
-template <typename F>
-int spin_until(nid_ctx *ctx, F arrived, unsigned long &spins, bool &synced, bool &waited) {
-  while (!arrived()) {
-    waited = true;
-    if (++spins > 50000000ul) {
-      if (synced) { ctx->last_error = "a cell's results never arrived"; return NID_ERR_HIP; }
-      NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-      NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-      synced = true;
-      spins = 0;
-    }
-  }
-  return NID_OK;
-}
-
-// One cell's quadratic form, from its record, ADDED to acc[0..28] -- exactly the 32-double block k_eval2's tail forms
-// (residual_and_huber + constructQuadraticForm: the same IEEE operations on the same values) and the same addition
-// sum_blocks_w0 performs.  Terms that are +0.0 by construction (an inactive cell's block, the b and H entries of a
-// cost-only block) are not added: an accumulator that starts at +0.0 never holds -0.0, so x + 0.0 is x, bit for bit.
-inline void huber_weights(double err, double delta, float dsqr, double &rho0, double &rho1) {
-  const double e2 = err * err;  // robust_kernel_impl.cpp:77-91 (float dsqr)
-  rho0 = e2; rho1 = 1.0;
-  if (!(e2 <= dsqr)) {
-    const double sqrte = std::sqrt(e2);
-    rho0 = 2 * sqrte * delta - dsqr;
-    rho1 = delta / sqrte;
-  }
-}
-
-// first half, from the record's early words (err, active flag): chi2 and the count; returns rho1 (0 for a level-1 edge)
-inline double add_record_cost(const double *rec, double delta, float dsqr, double *acc) {
-  if (rec[1] == 0.0) return 0.0;  // level-1 edge
-  double rho0, rho1;
-  huber_weights(rec[0], delta, dsqr, rho0, rho1);
-  acc[0] += rho0;
-  acc[28] += 1.0;
-  return rho1;
-}
-// second half, from the Jacobian words: b and the upper triangle of H
-inline void add_record_jac(const double *J, double err, double rho1, double *acc) {
-  for (int n = 0; n < 6; n++) acc[1 + n] += 0.0 - (rho1 * J[n]) * err;
-  int idx = 7;
-  for (int a = 0; a < 6; a++)
-    for (int b = a; b < 6; b++, idx++) acc[idx] += (J[a] * rho1) * J[b];
-}
-
-// the same sums with AVX-512 (nid_hostsum.cpp: host-only C++ next to this file; the same operations lane by lane)
-extern "C" __attribute__((visibility("hidden"))) int nid_hostsum_have_avx512(void);
-extern "C" __attribute__((visibility("hidden"))) void nid_hostsum_jac_avx512(const double *rec, double err, double rho1, double *acc);
-extern "C" __attribute__((visibility("hidden"))) int nid_hostsum_take_jac_avx512(double *rec, unsigned long long sentinel, int active, double err,
-                                                                                  double rho1, double *acc);
-
-#ifndef NID_DIRECT_AHEAD
-#define NID_DIRECT_AHEAD 24
-#endif
-#ifndef NID_DIRECT_HINT
-#define NID_DIRECT_HINT 3
-#endif
-constexpr int kDirectAhead = NID_DIRECT_AHEAD;
+constexpr int kDirectAhead = 24;                               // wait_direct's prefetch distance, in records (48 / 96 measured the same)
+constexpr unsigned long kSpinLimit = 50000000ul, kSeqWordSpinLimit = 20000000ul;  // idle polls before a wait asks the runtime
 constexpr std::chrono::milliseconds kResidentPatience(2);      // a resident request unanswered for this long: fallback
 constexpr std::chrono::milliseconds kResidentHostIdle(50);     // the host retires a kernel it has not used for this long ...
 constexpr long long kResidentIdleTicks = 20000000;             // ... the kernel leaves by itself after 200 ms (100 MHz ticks)
 
 int resident_fallback(nid_ctx *ctx, Slot &S);
 
+// What every wait does with a poll that found nothing.
+struct Idler {
+  nid_ctx *ctx;
+  unsigned long limit;  // idle polls before the streams are synchronised
+  const char *gave_up;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  unsigned long spins = 0, polls = 0;
+  bool synced = false;
+
+  // THE waiting rule: spin; after `limit` idle polls synchronise both streams once, so that a device error surfaces
+  // through the runtime.  Behind a synchronised stream a word has arrived or never will: the next idle poll gives up.
+  // (all three inlined into the waits' loops: an Idler whose address leaves the wait keeps its counters in memory)
+  __attribute__((always_inline)) int spin() {
+    if (!synced && ++spins <= limit) return NID_OK;
+    if (synced) { ctx->last_error = gave_up; return NID_ERR_HIP; }
+    NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
+    NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
+    synced = true;
+    return NID_OK;
+  }
+  template <typename F>
+  __attribute__((always_inline)) int until(F arrived) {
+    while (!arrived()) { int rc = spin(); if (rc) return rc; }
+    return NID_OK;
+  }
+  // ... and with a resident request in flight, RESIDENT PATIENCE instead: a resident kernel answers within
+  // microseconds; one that has left (its idle limit, a device-wide wait elsewhere) never will: every 1024 polls the
+  // clock is read, and after kResidentPatience the request is re-issued as an ordinary launch (resident_fallback) --
+  // *reissued: the wait starts over, as an ordinary one
+  __attribute__((always_inline)) int idle(Slot &S, bool *reissued) {
+    *reissued = false;
+    if (!is_resident(S)) return spin();
+    if ((++polls & 1023ul) != 0 || std::chrono::steady_clock::now() - t0 <= kResidentPatience) return NID_OK;
+    int rc = resident_fallback(ctx, S);
+    *reissued = rc == NID_OK;
+    return rc;
+  }
+};
+
+// the resident kernel has answered slot S's request
+void resident_served(nid_ctx *ctx, Slot &S) {
+  ctx->res.pending_slot = -1; ctx->res.served++; ctx->res.fallback_run = 0;
+  S.delivery = S.delivery == Delivery::ResidentCellout ? Delivery::Cellout : Delivery::Direct;
+}
+
+// DIRECT records (the slot's own, or the resident kernel's): a loop around DirectSum's step, which never waits.  Here:
+// the prefetch distance, the trace, and what to do while nothing has arrived.
 int wait_direct(nid_ctx *ctx, Slot &S) {
-  const int nloc = ctx->g.nloc, gs = ctx->group_size;
-  const float dsqr = (float)(S.direct_delta * S.direct_delta);  // RobustKernelHuber::setDelta (robust_kernel_impl.h:84)
+  const int nloc = ctx->g.nloc;
   const bool jac = S.direct_jac;
   static const bool trace = getenv("NID_DIRECT_TRACE") != nullptr;
   static const bool vec512 = nid_hostsum_have_avx512() != 0 && getenv("NID_DIRECT_SCALAR") == nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
   std::vector<double> &hub = ctx->direct_rho1;  // per cell: rho1, err, active
   if (jac && hub.size() < (size_t)3 * nloc) hub.resize((size_t)3 * nloc);
+  Idler idler{ctx, kSpinLimit, "a cell's results never arrived"};
   for (;;) {  // (a second round only after a resident kernel had to be replaced by an ordinary launch)
-    double *base = S.resident ? ctx->res.rec_host : S.quad_host;
-    // Two cursors over the cells, each in cell order.  c1: residual records (a cost + Jacobian kernel sends them
-    // BEFORE its Jacobian phase, so this work -- a square root and a division per cell -- is done while the device is
-    // still busy) -> Huber weights, chi2 (entry 0), count (entry 28).  c2 <= c1: Jacobian records -> b, H (entries
-    // 1..27).  Every entry has its own chain of additions, in sum_blocks_w0's order, whichever cursor performs it:
-    // per group the even-numbered cells in ascending order plus the odd-numbered ones, then the groups likewise.
-    alignas(64) double top[2][32] = {}, grp[2][32] = {};
-    double g00[2] = {0.0, 0.0}, g28[2] = {0.0, 0.0};
-    int c1 = 0, c2 = jac ? 0 : nloc;
-    unsigned long spins = 0, patience = 0;
-    bool synced = false, again = false;
-    auto t_first = t0, t_lastwait = t0;
-    bool got_first = false, waited = false;
-    while (c1 < nloc || c2 < nloc) {
-      if (c1 < nloc) {
-        double *rec = base + (size_t)c1 * kDirectRec;
-        if (words_arrived(rec, kDirectRec)) {
-          // every record is a line the device has just written, i.e. a miss to memory: ask for the lines ahead
-          if (c1 + kDirectAhead < nloc) __builtin_prefetch(rec + (size_t)kDirectAhead * kDirectRec, 0, NID_DIRECT_HINT);
-          __atomic_thread_fence(__ATOMIC_ACQUIRE);  // (the words were read as volatile; keep the plain reads below behind them)
-          const int i = c1 % gs, gq = c1 / gs;
-          double acc[32];
-          acc[0] = g00[i & 1]; acc[28] = g28[i & 1];
-          const double r1 = add_record_cost(rec, S.direct_delta, dsqr, acc);
-          g00[i & 1] = acc[0]; g28[i & 1] = acc[28];
-          if (jac) { double *w = &hub[3 * (size_t)c1]; w[0] = r1; w[1] = rec[0]; w[2] = rec[1]; }
-          fill_sentinel(rec, kDirectRec);
-          c1++;
-          if (i == gs - 1 || c1 == nloc) {  // the group is complete
-            top[gq & 1][0] += g00[0] + g00[1];
-            top[gq & 1][28] += g28[0] + g28[1];
-            g00[0] = g00[1] = g28[0] = g28[1] = 0.0;
-          }
-          if (trace && !jac) {
-            if (!got_first) { t_first = std::chrono::steady_clock::now(); got_first = true; }
-            if (waited) t_lastwait = std::chrono::steady_clock::now();
-          }
-          waited = false;
-          continue;
+    DirectSum::Blocks blocks;
+    DirectSum sum(blocks, is_resident(S) ? ctx->res.rec_host : S.quad_host, nloc, ctx->group_size, jac, S.direct_delta, hub.data(), vec512, kDirectAhead);
+    auto t_first = idler.t0, t_lastwait = idler.t0;
+    bool got_first = false, waited = false, reissued = false;
+    while (!sum.done() && !reissued) {
+      const DirectSum::Took took = sum.step();
+      if (took) {
+        if (trace && (took == DirectSum::kJacobian || !jac)) {
+          if (!got_first) { t_first = std::chrono::steady_clock::now(); got_first = true; }
+          if (waited) t_lastwait = std::chrono::steady_clock::now();
         }
+        waited = false;
+        continue;
       }
-      if (c2 < c1) {
-        double *rec = base + (size_t)(nloc + c2) * kDirectRec;
-        const int i = c2 % gs, gq = c2 / gs;
-        const double *w = &hub[3 * (size_t)c2];
-        bool took;
-        if (vec512) {  // arrival test, sums and re-arming on one load of the line (nid_hostsum.cpp)
-          took = nid_hostsum_take_jac_avx512(rec, kHostSentinel, w[2] != 0.0, w[1], w[0], grp[i & 1]) != 0;
-          if (took && c2 + kDirectAhead < nloc) __builtin_prefetch(rec + (size_t)kDirectAhead * kDirectRec, 0, NID_DIRECT_HINT);
-        } else {
-          took = words_arrived(rec, kDirectRec);
-          if (took) {
-            if (c2 + kDirectAhead < nloc) __builtin_prefetch(rec + (size_t)kDirectAhead * kDirectRec, 0, NID_DIRECT_HINT);
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            if (w[2] != 0.0) add_record_jac(rec, w[1], w[0], grp[i & 1]);
-            fill_sentinel(rec, kDirectRec);
-          }
-        }
-        if (took) {
-          c2++;
-          if (i == gs - 1 || c2 == nloc) {
-            double *t = top[gq & 1];
-            for (int v = 1; v < 28; v++) t[v] += grp[0][v] + grp[1][v];
-            std::memset(grp, 0, sizeof(grp));
-          }
-          if (trace) {
-            if (!got_first) { t_first = std::chrono::steady_clock::now(); got_first = true; }
-            if (waited) t_lastwait = std::chrono::steady_clock::now();
-          }
-          waited = false;
-          continue;
-        }
-      }
-      // nothing to do yet
-      waited = true;
-      if (S.resident) {
-        // a resident kernel answers within microseconds; one that has left (its idle limit, a device-wide wait
-        // elsewhere) never will: after kResidentPatience the request is re-issued as an ordinary DIRECT launch
-        if ((++patience & 1023ul) == 0 && std::chrono::steady_clock::now() - t0 > kResidentPatience) {
-          int rc = resident_fallback(ctx, S);
-          if (rc) return rc;
-          again = true;
-          break;
-        }
-      } else if (++spins > 50000000ul) {  // let a device error surface through the runtime, then give up
-        if (synced) { ctx->last_error = "a cell's results never arrived"; return NID_ERR_HIP; }
-        NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-        NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-        synced = true;
-        spins = 0;
-      }
+      waited = true;  // nothing to do yet
+      int rc = idler.idle(S, &reissued);
+      if (rc) return rc;
     }
-    if (again) continue;
-    for (int v = 0; v < kReducedLen; v++) S.reduced_host[v] = v < 29 ? top[0][v] + top[1][v] : 0.0;
+    if (reissued) continue;
+    sum.finish(S.reduced_host);
     if (trace) {
       const auto t1 = std::chrono::steady_clock::now();
-      auto us = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::micro>(t - t0).count(); };
+      auto us = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::micro>(t - idler.t0).count(); };
       g_dtrace.first += us(t_first); g_dtrace.last_wait += us(t_lastwait); g_dtrace.end += us(t1);
       if (++g_dtrace.n % 2000 == 0) {
         fprintf(stderr, "[direct trace] %ld waits: first %s record %.2f us, last wait %.2f us, end %.2f us after entering the wait\n", g_dtrace.n,
@@ -749,58 +638,66 @@ int wait_direct(nid_ctx *ctx, Slot &S) {
     }
     break;
   }
-  if (S.resident) { ctx->res.pending_slot = -1; ctx->res.served++; ctx->res.fallback_run = 0; S.resident = false; }
+  if (is_resident(S)) resident_served(ctx, S);
   else S.quad_dirty = false;
   return NID_OK;
 }
 
+// GROUP-DIRECT (nid_set_direct_results(ctx, 2)): the whole per-cell tail stays on the device -- Huber kernel, quadratic
+// form, and the first level of the reduction (every group's last workgroup sums its group's blocks) -- and the group
+// sums go straight to pinned host memory, one 256-byte block per group; the host adds the <= 32 group blocks in
+// sum_blocks_w0's order (the second level: even-numbered groups ascending plus the odd-numbered ones).  Against the
+// in-launch reduction it saves the second ticket round trip, the re-read of the group sums and the system-scope fence;
+// against DIRECT it keeps a15 on the GPU and costs the first ticket round trip.  Same bits as both.
 int wait_groups(nid_ctx *ctx, Slot &S) {
-  const int ngroups = (ctx->g.nloc + ctx->group_size - 1) / ctx->group_size;
-  alignas(64) double top[2][32] = {};
-  unsigned long spins = 0;
-  bool synced = false, waited = false;
+  const int ngroups = ctx->ngroups;
+  alignas(64) double top[2][kSumBlock] = {};
+  Idler idler{ctx, kSpinLimit, "a cell's results never arrived"};
   for (int gq = 0; gq < ngroups; gq++) {
     double *blk = S.groups_host + (size_t)gq * kQuad;
-    int rc = spin_until(ctx, [&] { return words_arrived(blk, kQuad); }, spins, synced, waited);
+    int rc = idler.until([&] { return words_arrived(blk, kQuad); });
     if (rc) return rc;
     if (gq + 2 < ngroups) __builtin_prefetch(blk + 2 * kQuad, 0, 3);
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    double *t = top[gq & 1];
-    for (int v = 0; v < kQuad; v++) t[v] += blk[v];
+    add_block(top, gq, blk, 0, kQuad);
     fill_sentinel(blk, kQuad);
   }
-  for (int v = 0; v < kReducedLen; v++) S.reduced_host[v] = top[0][v] + top[1][v];
+  sum_halves(top, 0, kReducedLen, S.reduced_host);
   S.groups_dirty = false;
   return NID_OK;
 }
 
-// the per-cell calls: every cell's kCellOut outputs, word by word
+// the per-cell calls: every cell's kCellOut outputs, word by word (a request that was re-issued starts over: its
+// outputs were wiped)
 int wait_direct_cellout(nid_ctx *ctx, Slot &S) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    unsigned long spins = 0;
-    bool synced = false, waited = false, again = false;
-    for (int cl = 0; cl < ctx->g.nloc && !again; cl++) {
-      const double *co = S.cellout_host + (size_t)cl * kCellOut;
-      if (S.resident) {
-        unsigned long n = 0;
-        while (!words_arrived(co, kCellOut)) {
-          if ((++n & 1023ul) == 0 && std::chrono::steady_clock::now() - t0 > kResidentPatience) {
-            int rc = resident_fallback(ctx, S);
-            if (rc) return rc;
-            again = true;
-            break;
-          }
-        }
-      } else {
-        int rc = spin_until(ctx, [&] { return words_arrived(co, kCellOut); }, spins, synced, waited);
-        if (rc) return rc;
-      }
-    }
-    if (!again) break;
+  Idler idler{ctx, kSpinLimit, "a cell's results never arrived"};
+  for (int cl = 0; cl < ctx->g.nloc;) {
+    if (words_arrived(S.cellout_host + (size_t)cl * kCellOut, kCellOut)) { cl++; continue; }
+    bool reissued;
+    int rc = idler.idle(S, &reissued);
+    if (rc) return rc;
+    if (reissued) cl = 0;
   }
   __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  if (S.resident) { ctx->res.pending_slot = -1; ctx->res.served++; ctx->res.fallback_run = 0; S.resident = false; }
+  if (is_resident(S)) resident_served(ctx, S);
+  return NID_OK;
+}
+
+// spin on the sequence word the last workgroup of slot S's launch writes behind its results (system-scope release)
+int wait_host_seq(nid_ctx *ctx, Slot &S) {
+  volatile unsigned long long *seqw = reinterpret_cast<volatile unsigned long long *>(S.reduced_host + kReducedLen);
+  Idler idler{ctx, kSeqWordSpinLimit, "result sequence word never arrived"};
+  return idler.until([&] { return __atomic_load_n(seqw, __ATOMIC_ACQUIRE) == S.seq; });
+}
+
+// the per-pixel dump of a diagnostic launch starts from all-ones
+int clear_pixel_dump(nid_ctx *ctx, hipStream_t stream) {
+  const size_t N = (size_t)ctx->g.rows * ctx->g.cols;
+  NID_HIP(ctx, hipMemsetAsync(ctx->dbg_u, 0xFF, N * 8, stream));
+  NID_HIP(ctx, hipMemsetAsync(ctx->dbg_v, 0xFF, N * 8, stream));
+  NID_HIP(ctx, hipMemsetAsync(ctx->dbg_ic, 0xFF, N * 8, stream));
+  NID_HIP(ctx, hipMemsetAsync(ctx->dbg_wc, 0xFF, N * 32, stream));
+  NID_HIP(ctx, hipMemsetAsync(ctx->dbg_jc, 0xFF, N * 4, stream));
   return NID_OK;
 }
 
@@ -841,50 +738,43 @@ int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double d
   if (S.pending) return refuse_pending(ctx);
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   S.seq++;
-  S.external_target = reduced_target != nullptr;
-  double *target = S.external_target ? static_cast<double *>(reduced_target) : S.reduced_host_devptr;
-  unsigned long long *host_seq =
-      S.external_target ? nullptr : reinterpret_cast<unsigned long long *>(S.reduced_host_devptr + kReducedLen);
+  const bool external = reduced_target != nullptr;
+  double *target = external ? static_cast<double *>(reduced_target) : S.reduced_host_devptr;
+  unsigned long long *host_seq = external ? nullptr : reinterpret_cast<unsigned long long *>(S.reduced_host_devptr + kReducedLen);
   EvalParams P{};
   fill_eval_params(ctx, pose, S, delta, target, host_seq, &P);
-  S.direct = S.resident = S.groups = false;
-  if (!S.external_target && direct_ok(ctx)) {
-    S.direct = true;
+  // the route home: a caller-owned buffer's event; with DIRECT results the resident kernel (no launch at all),
+  // GROUP-DIRECT or DIRECT records; otherwise the sequence word
+  Delivery route = external ? Delivery::Event : Delivery::SeqWord;
+  if (!external && direct_ok(ctx)) {
     S.direct_jac = want_jac != 0;
     S.direct_delta = delta;
-    const bool groups = ctx->direct_mode == 2 && !on_aux_stream;
-    if (!groups && !on_aux_stream && resident_usable(ctx) && resident_post(ctx, slot, pose, want_jac != 0, false) == NID_OK) {
-      S.resident = true;  // no launch at all: the resident kernel has the request
-      S.timed = false;
-      S.done_slot = slot;
-      S.pending = true;
-      return NID_OK;
-    }
-    if (groups) {  // GROUP-DIRECT: the in-launch tail up to the group sums, those straight to the host
-      rc = ensure_groups_host(ctx, S);
-      if (rc) return rc;
-      P.slot[0].out_reduced = S.groups_host_devptr;
-      P.slot[0].host_seq = nullptr;
-      P.slot[0].host_quad = 3;
-      S.direct = false;
-      S.groups = true;
-      S.groups_dirty = true;
-    } else {
-      rc = ensure_quad_host(ctx, S);
-      if (rc) return rc;
-      P.slot[0].quad = S.quad_host_devptr;
-      P.slot[0].host_quad = 1;
-      S.quad_dirty = true;
-    }
+    route = ctx->direct_mode == 2 && !on_aux_stream ? Delivery::Groups : Delivery::Direct;
+    if (route == Delivery::Direct && !on_aux_stream && resident_usable(ctx) && resident_post(ctx, slot, pose, want_jac != 0, false) == NID_OK)
+      route = Delivery::ResidentRecords;
   }
-  if (ctx->dbg_enabled) {
-    const size_t N = (size_t)ctx->g.rows * ctx->g.cols;
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_u, 0xFF, N * 8, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_v, 0xFF, N * 8, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_ic, 0xFF, N * 8, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_wc, 0xFF, N * 32, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_jc, 0xFF, N * 4, ctx->stream));
+  S.delivery = route;
+  if (route == Delivery::ResidentRecords) {
+    S.timed = false;
+    S.done_slot = slot;
+    S.pending = true;
+    return NID_OK;
   }
+  if (route == Delivery::Groups) {  // the in-launch tail up to the group sums, those straight to the host
+    rc = ensure_host_words(ctx, S.groups_host, S.groups_host_devptr, S.groups_dirty, (size_t)ctx->ngroups * kQuad);
+    if (rc) return rc;
+    P.slot[0].out_reduced = S.groups_host_devptr;
+    P.slot[0].host_seq = nullptr;
+    P.slot[0].host_quad = 3;
+    S.groups_dirty = true;
+  } else if (route == Delivery::Direct) {
+    rc = ensure_quad_host(ctx, S);
+    if (rc) return rc;
+    P.slot[0].quad = S.quad_host_devptr;
+    P.slot[0].host_quad = 1;
+    S.quad_dirty = true;
+  }
+  if (ctx->dbg_enabled) { rc = clear_pixel_dump(ctx, ctx->stream); if (rc) return rc; }
   // single-pose launches stay on one in-order stream (alternating streams per single-pose launch measured
   // 2.2x slower); the batched pipeline of nid_run_sequence is the one that alternates
   hipStream_t st = (on_aux_stream && !ctx->external_stream) ? ctx->aux_stream : ctx->stream;
@@ -893,7 +783,7 @@ int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double d
   if (S.timed) NID_HIP(ctx, hipEventRecord(S.e0, st));
   rc = launch_eval2(ctx, P, want_jac != 0, st, 1, S.timed ? S.e1 : nullptr);  // (timed: e1 right behind k_eval2, in front of k_repair)
   if (rc) return rc;
-  if (S.external_target) NID_HIP(ctx, hipEventRecord(S.done, st));
+  if (external) NID_HIP(ctx, hipEventRecord(S.done, st));
   S.done_slot = slot;
   S.pending = true;
   return NID_OK;
@@ -920,6 +810,7 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   // up to kMaxBatch poses: the per-pose records are kernel arguments; beyond: a device array from the ring
   int ring = -1;
   SlotArgs *recs = P.slot;
+  const bool external = reduced_dev_base != nullptr;
   if (n > kMaxBatch) {
     ring = ctx->ext_next;
     ctx->ext_next = (ctx->ext_next + 1) % nid_ctx::kExtRing;
@@ -932,9 +823,8 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   for (int k = 0; k < n; k++) {
     Slot &S = ctx->slots[first_slot + k];
     S.seq++;
-    S.direct = S.resident = false;
-    S.external_target = reduced_dev_base != nullptr;
-    if (S.external_target) {  // caller-owned device buffer: pose k's block at base + k*32 (the pipelined loops, multi-GPU all-reduce)
+    S.delivery = external ? Delivery::Event : Delivery::SeqWord;
+    if (external) {  // caller-owned device buffer: pose k's block at base + k*32 (the pipelined loops, multi-GPU all-reduce)
       fill_slot_args(ctx, poses[k], S, reduced_dev_base + (size_t)k * kReducedLen, nullptr, &recs[k]);
       if (n > kMaxBatch) recs[k].cellout = nullptr;  // nobody reads the per-cell outputs of such a launch
     }
@@ -954,7 +844,7 @@ int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   }
   // caller-owned result buffer: the launch is over when its ONE event is (recorded on the batch's first slot; the
   // other slots point at it -- an event record per pose cost ~4 us each, 1 ms of host time per 256-pose launch)
-  if (S0.external_target) NID_HIP(ctx, hipEventRecord(S0.done, st));
+  if (external) NID_HIP(ctx, hipEventRecord(S0.done, st));
   for (int k = 0; k < n; k++) {
     Slot &S = ctx->slots[first_slot + k];
     S.pending = true;
@@ -1015,25 +905,6 @@ int launch_split(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int wan
   return NID_OK;
 }
 
-// spin on the sequence word the last workgroup of slot S's launch writes behind its results (system-scope release)
-int wait_host_seq(nid_ctx *ctx, Slot &S) {
-  volatile unsigned long long *seqw = reinterpret_cast<volatile unsigned long long *>(S.reduced_host + kReducedLen);
-  unsigned long spins = 0;
-  while (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != S.seq) {
-    if (++spins > 20000000ul) {  // fall back to the runtime so that a device error surfaces
-      NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-      NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-      if (__atomic_load_n(seqw, __ATOMIC_ACQUIRE) != S.seq) {
-        ctx->last_error = "result sequence word never arrived";
-        return NID_ERR_HIP;
-      }
-      break;
-    }
-  }
-  return NID_OK;
-}
-
 int evaluate_common(nid_ctx *ctx, const Pose &pose, int want_jac, double *Ht, double *Hj,
                     double *err, double *der) {
   int rc = check_ready(ctx);
@@ -1047,32 +918,25 @@ int evaluate_common(nid_ctx *ctx, const Pose &pose, int want_jac, double *Ht, do
   // slot's sequence word behind them (as for the fused 6x6 path): no copy, no stream synchronisation -- the call
   // returns ~6 us after the kernel ends instead of ~18.
   S.seq++;
-  S.external_target = false;
   EvalParams P{};
   fill_eval_params(ctx, pose, S, std::sqrt(0.95), S.reduced_host_devptr,
                    reinterpret_cast<unsigned long long *>(S.reduced_host_devptr + kReducedLen), &P);
   P.slot[0].cellout = S.cellout_host_devptr;
   P.slot[0].cellout_host = 1;
-  const bool direct = direct_ok(ctx);
-  S.resident = false;
-  if (direct) {  // the per-cell outputs straight to the host, word by word, and nothing else (wait_direct_cellout)
+  Delivery route = Delivery::SeqWord;
+  if (direct_ok(ctx)) {  // the per-cell outputs straight to the host, word by word, and nothing else (wait_direct_cellout)
     fill_sentinel(S.cellout_host, (size_t)ctx->g.nloc * kCellOut);
     P.slot[0].host_quad = 2;
-    if (resident_usable(ctx) && resident_post(ctx, 0, pose, want_jac != 0, true) == NID_OK) S.resident = true;
+    const bool posted = resident_usable(ctx) && resident_post(ctx, 0, pose, want_jac != 0, true) == NID_OK;
+    route = posted ? Delivery::ResidentCellout : Delivery::Cellout;
   }
-  if (ctx->dbg_enabled) {
-    const size_t N = (size_t)ctx->g.rows * ctx->g.cols;
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_u, 0xFF, N * 8, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_v, 0xFF, N * 8, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_ic, 0xFF, N * 8, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_wc, 0xFF, N * 32, ctx->stream));
-    NID_HIP(ctx, hipMemsetAsync(ctx->dbg_jc, 0xFF, N * 4, ctx->stream));
-  }
-  if (!S.resident) {
+  S.delivery = route;
+  if (ctx->dbg_enabled) { rc = clear_pixel_dump(ctx, ctx->stream); if (rc) return rc; }
+  if (route != Delivery::ResidentCellout) {
     rc = launch_eval2(ctx, P, want_jac != 0, ctx->stream);
     if (rc) return rc;
   }
-  rc = direct ? wait_direct_cellout(ctx, S) : wait_host_seq(ctx, S);
+  rc = route == Delivery::SeqWord ? wait_host_seq(ctx, S) : wait_direct_cellout(ctx, S);
   if (rc) return rc;
   if (ctx->dbg_enabled) NID_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the dump is read back by the runtime
   for (int cl = 0; cl < ctx->g.nloc; cl++) {
@@ -1354,7 +1218,7 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   const size_t N = (size_t)g.rows * g.cols;
   const size_t plane = (size_t)g.nloc * g.pstride;
   // two-level reduction geometry: ~sqrt(nloc) cells per group
-  ctx->group_size = std::max(1, (int)std::ceil(std::sqrt((double)g.nloc)));
+  ctx->group_size = direct_group_size(g.nloc);
   ctx->ngroups = (g.nloc + ctx->group_size - 1) / ctx->group_size;
   ctx->sz = pose_sizes(g.nloc, ctx->ngroups);
   int rc;
@@ -2057,22 +1921,22 @@ int nid_wait(nid_ctx *ctx, int slot, double *H36, double *b6, double *chi2, int3
   if (!S.pending) return NID_ERR_STATE;
   // `pending` is cleared only once the result is known to have arrived: after an error the slot stays
   // pending (a retry is possible, a relaunch is refused)
-  if (S.external_target) {
-    NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-    NID_HIP(ctx, hipEventSynchronize(ctx->slots[S.done_slot].done));
-    S.pending = false;
-    return NID_OK;
+  int rc = NID_OK;
+  switch (S.delivery) {
+    case Delivery::Event:  // the result is the caller's, in its own buffer
+      NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
+      NID_HIP(ctx, hipEventSynchronize(ctx->slots[S.done_slot].done));
+      S.pending = false;
+      return NID_OK;
+    case Delivery::SeqWord: rc = wait_host_seq(ctx, S); break;  // the last workgroup stores the 32 results, then the sequence word
+    case Delivery::Direct:
+    case Delivery::ResidentRecords: rc = wait_direct(ctx, S); break;  // the host collects the cells' records and sums their quadratic forms
+    case Delivery::Groups: rc = wait_groups(ctx, S); break;
+    case Delivery::Collected: break;
+    case Delivery::Cellout:
+    case Delivery::ResidentCellout: return NID_ERR_STATE;  // (the per-cell calls are blocking: never pending)
   }
-  // the last workgroup stores the 32 results, then the sequence word (system-scope release); DIRECT launches: the
-  // host collects the cells' records and sums their quadratic forms
-  if (S.collected) {
-    S.collected = false;
-  } else {
-    int rc = S.direct ? wait_direct(ctx, S) : (S.groups ? wait_groups(ctx, S) : wait_host_seq(ctx, S));
-    if (rc) return rc;
-  }
-  S.direct = false;
-  S.groups = false;
+  if (rc) return rc;
   S.pending = false;
   return nid_unpack_reduced(S.reduced_host, H36, b6, chi2, n_active);
 }

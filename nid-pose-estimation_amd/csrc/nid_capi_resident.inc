@@ -218,8 +218,6 @@ int resident_post(nid_ctx *ctx, int slot, const Pose &pose, bool jac, bool want_
 // registers each on every CU they sit on: a launch whose workgroups do not fit beside them would wait until the
 // resident kernel leaves by itself.  So it leaves now -- after the request it may be working on has been collected
 // (its slot keeps the result for nid_wait).
-int wait_host_seq(nid_ctx *ctx, Slot &S);
-
 int resident_quiesce(nid_ctx *ctx) {
   nid_ctx::Resident &R = ctx->res;
   if (!R.running) return NID_OK;
@@ -227,8 +225,7 @@ int resident_quiesce(nid_ctx *ctx) {
     Slot &S = ctx->slots[R.pending_slot];
     int rc = wait_direct(ctx, S);  // (the per-cell calls are blocking: never pending here)
     if (rc) return rc;
-    S.direct = false;
-    S.collected = true;
+    S.delivery = Delivery::Collected;
   }
   resident_retire(ctx);
   return NID_OK;
@@ -264,7 +261,7 @@ int resident_fallback(nid_ctx *ctx, Slot &S) {
   S.quad_dirty = !R.want_cellout;
   if (R.want_cellout) { A.cellout = ctx->slots[0].cellout_host_devptr; A.cellout_host = 1; }
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-  S.resident = false;  // from here on the wait is an ordinary DIRECT wait
+  S.delivery = R.want_cellout ? Delivery::Cellout : Delivery::Direct;  // from here on the wait is an ordinary one
   R.pending_slot = -1;
   return launch_eval2(ctx, P, R.jac, ctx->stream);
 }

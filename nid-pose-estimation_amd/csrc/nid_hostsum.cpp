@@ -1,4 +1,4 @@
-// nid_hostsum.cpp -- host side of the DIRECT results (nid_capi.hip, wait_direct): one cell's Jacobian record added to the
+// nid_hostsum.cpp -- host side of the DIRECT results (nid_direct_sum.h, DirectSum::step): one cell's Jacobian record added to the
 // 27 running sums b[6], H upper[21] of the normal equations, with AVX-512 where the host CPU has it.
 // The sums are what the in-launch reduction forms (sum_blocks_w0 in nid_kernels.hip.h): per entry (J[a] * rho1) * J[b],
 // resp. 0.0 - (rho1 * J[n]) * err, IEEE mul / sub / add in that order -- the vector lanes do exactly the scalar

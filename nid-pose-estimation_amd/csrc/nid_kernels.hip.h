@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "nid_bspline.h"
+#include "nid_direct_sum.h"  // kDirectRec, kHostSentinel: the DIRECT records' layout, shared with the host's sums (no HIP in it)
 
 // 1: clamped target samples are summed per reference bin and folded in with their constant weights (kClampBins)
 #ifndef NID_CLAMP_BINS
@@ -118,11 +119,7 @@ struct SlotArgs {
                                    // 3: GROUP-DIRECT -- the in-launch tail up to the group sums, which go to `out_reduced` =
                                    // mapped pinned host memory [ngroups][32] (the host adds the groups up)
 };
-// A cell's records of a DIRECT launch, one 64-byte line each, every line written by ONE store instruction (a line
-// written in two instalments sat in a write combiner for ~30 us):
-//   residual record [cl]:        err | 1.0 active / 0.0 level-1 edge | 0 x 6   -- sent when the cost phase is over
-//   Jacobian record [nloc + cl]: J[6] | 0 | 0                                   -- cost + Jacobian launches only
-constexpr int kDirectRec = 8;
+// (a cell's records of a DIRECT launch -- kDirectRec words each -- and the host's sentinel: nid_direct_sum.h)
 
 struct EvalParams {
   Geometry g;
@@ -717,9 +714,6 @@ __device__ __forceinline__ void store_sys(double *p, double v) {
   __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v),
                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// The bit pattern the host fills a DIRECT launch's result words with before the launch (a signalling-NaN payload no
-// arithmetic produces: NaN results are the canonical quiet NaN); a word that still holds it has not arrived.
-constexpr unsigned long long kHostSentinel = 0x7FF4DEADBEEF5A5Aull;
 
 // 128- / 256-thread shapes: the six sums go through a [6][kXposeStride] array of doubles that reuses the histogram area
 // (rows padded by 8 doubles so that the six row groups of a read do not share banks); 0 = the DPP form everywhere

@@ -801,7 +801,7 @@ int nid_multi_run_sequence(nid_multi *m, const double *poses7, int n, int batch,
       (void)hipGetLastError();
       for (int s = 0; s < NID_SLOTS; s++) {
         Slot &S = ctx->slots[s];
-        if (S.pending && S.external_target) S.pending = false;
+        if (S.pending && S.delivery == Delivery::Event) S.pending = false;
       }
       for (int i = 0; i < kGroupRing; i++) m->buf[k].ring_used[i] = false;
     }

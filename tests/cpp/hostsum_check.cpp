@@ -1,27 +1,19 @@
 // tests/cpp/hostsum_check.cpp -- csrc/nid_hostsum.cpp (the AVX-512 sums of the DIRECT results) against the scalar loop of
-// csrc/nid_capi.hip (add_record_jac), bit for bit, on random records: plain values, zeros, signed zeros, huge and tiny
-// magnitudes, inactive cells, records that have not arrived.  Built and run by tests/test_host_cpu.py (skipped on a CPU
-// without AVX-512).  Exit code 0 = identical, 1 = mismatch, 2 = no AVX-512 here.
+// csrc/nid_direct_sum.h (add_record_jac: the library's own, included here), bit for bit, on random records: plain values,
+// zeros, signed zeros, huge and tiny magnitudes, inactive cells, records that have not arrived.  Built and run by
+// tests/test_host_cpu.py (skipped on a CPU without AVX-512).  Exit code 0 = identical, 1 = mismatch, 2 = no AVX-512 here.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <random>
 
-extern "C" int nid_hostsum_have_avx512(void);
-extern "C" void nid_hostsum_jac_avx512(const double *rec, double err, double rho1, double *acc);
-extern "C" int nid_hostsum_take_jac_avx512(double *rec, unsigned long long sentinel, int active, double err, double rho1, double *acc);
+#include "nid_direct_sum.h"  // add_record_jac, kHostSentinel, and the declarations of nid_hostsum.cpp's functions
 
-// the scalar form, as in nid_capi.hip
-static void add_record_jac(const double *J, double err, double rho1, double *acc) {
-  for (int n = 0; n < 6; n++) acc[1 + n] += 0.0 - (rho1 * J[n]) * err;
-  int idx = 7;
-  for (int a = 0; a < 6; a++)
-    for (int b = a; b < 6; b++, idx++) acc[idx] += (J[a] * rho1) * J[b];
-}
+using nid::add_record_jac;
 
 int main() {
   if (!nid_hostsum_have_avx512()) { std::puts("no AVX-512 on this CPU"); return 2; }
-  const unsigned long long sentinel = 0x7FF4DEADBEEF5A5Aull;
+  const unsigned long long sentinel = nid::kHostSentinel;
   std::mt19937_64 rng(12345);
   std::uniform_real_distribution<double> uni(-1.0, 1.0);
   alignas(64) double acc_s[32] = {}, acc_v[32] = {}, acc_t[32] = {}, rec[8], rec2[8];

@@ -367,7 +367,7 @@ def test_driver_refuses_cpu_mode(tmp_path):
 @pytest.mark.parametrize("compiler", ["g++", "/opt/rocm/lib/llvm/bin/clang++"])
 def test_direct_results_avx512_sums_equal_the_scalar_loop(tmp_path, compiler):
     """csrc/nid_hostsum.cpp (the host's part of a DIRECT launch on a CPU with AVX-512: one load per record -- arrival
-    test, the 27 products of the normal equations, re-arming) against the scalar loop of csrc/nid_capi.hip, bit for bit
+    test, the 27 products of the normal equations, re-arming) against the scalar loop of csrc/nid_direct_sum.h, bit for bit
     on 200 000 random records (zeros, signed zeros, 600 binades of magnitudes, inactive cells, records with a word still
     missing); built WITHOUT -ffp-contract=off on purpose: the file must not depend on the library's build flags.
     No GPU involved; tests/test_parity_gpu.py::test_direct_results_equal_in_launch_reduction is the end-to-end check."""
@@ -376,12 +376,36 @@ def test_direct_results_avx512_sums_equal_the_scalar_loop(tmp_path, compiler):
     if not (shutil.which(compiler) or os.path.exists(compiler)):
         pytest.skip(f"{compiler} not available")
     exe = str(tmp_path / "hostsum_check")
-    subprocess.check_call([compiler, "-O2", "-std=c++17", "-o", exe, os.path.join(root, "tests", "cpp", "hostsum_check.cpp"),
+    subprocess.check_call([compiler, "-O2", "-std=c++17", "-I", os.path.join(root, "nid-pose-estimation_amd", "csrc"), "-o", exe,
+                           os.path.join(root, "tests", "cpp", "hostsum_check.cpp"),
                            os.path.join(root, "nid-pose-estimation_amd", "csrc", "nid_hostsum.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     if r.returncode == 2:
         pytest.skip("no AVX-512 on this CPU: the library takes the scalar loop here")
     assert r.returncode == 0, r.stdout[-2000:]
+
+
+def test_direct_sums_equal_the_in_launch_order_for_every_arrival_order(tmp_path):
+    """csrc/nid_direct_sum.h (the host's half of a DIRECT launch: Huber weights with the float dsqr, per-cell quadratic
+    forms, the two cursors that reproduce sum_blocks_w0's order; plain arithmetic, no HIP) through its non-blocking step
+    against tests/cpp/direct_sum_check.cpp's independently written reference -- every cell's 32-double block, then the
+    even-plus-odd rule per group and over the groups -- bit for bit: 1 .. 1024 cells (partial last groups), cost +
+    Jacobian and cost only, residuals on, beside and far from the Huber threshold, inactive cells / groups / everything,
+    zeros, signed zeros and 300 binades of Jacobians; records present at once, in cell order, Jacobian before residual,
+    and word by word in a random order (an incomplete record is never taken; every record is re-armed).  A stand-alone
+    program under AddressSanitizer + UndefinedBehaviorSanitizer, the scalar path always and the AVX-512 one where the CPU
+    has it.  tests/test_parity_gpu.py::test_direct_results_equal_in_launch_reduction is the end-to-end check."""
+    exe = tmp_path / "direct_sum_check"
+    csrc = os.path.join(ROOT, "nid-pose-estimation_amd", "csrc")
+    subprocess.check_call(["g++", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-O1", "-g", "-std=c++17", "-Wall", "-Werror",
+                           "-I", csrc, os.path.join(ROOT, "tests", "cpp", "direct_sum_check.cpp"), os.path.join(csrc, "nid_hostsum.cpp"),
+                           "-o", str(exe)])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
+    env.pop("LD_PRELOAD", None)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
+    m = re.search(r"direct sum: (\d+) cases \((\d+) sizes with a partial last group, [^)]*\), 0 failures", r.stdout)
+    assert m and int(m.group(1)) >= 9 * 4 * 2 * 4 and int(m.group(2)) >= 3, r.stdout
 
 
 def test_fused_grid_budget_rule_matches_hand_derived_values(tmp_path):
