@@ -23,6 +23,9 @@
  * Out of scope: cell shards (cfg0 must own all cells), levels on different devices, a device-side selection of the
  * survivors (a handful of comparisons on the host between two blocking calls), and a reference stage inside
  * nid_pyr_set_pair_u16.
+ *
+ * Frame streams on the same object -- a new target alone, the target promoted to the reference, a tracker -- are a header
+ * of their own: nid/nid_pyr_stream.h.
  */
 #ifndef NID_PYR_H
 #define NID_PYR_H

@@ -78,6 +78,23 @@ PYR_SYMBOLS = ["nid_pyr_level_config", "nid_pyr_create", "nid_pyr_destroy", "nid
                "nid_pyr_set_pair_u16", "nid_pyr_get_level_inputs", "nid_pyr_multistart_lm"]
 PYR_MAX_LEVELS = 8
 
+# include/nid/nid_pyr_stream.h (a header of its own again: frame streams on the resident pyramid, pose helpers, a tracker)
+STREAM_SYMBOLS = ["nid_pyr_set_target_u8", "nid_pyr_promote_target_u16",
+                  "nid_track_pose_inverse", "nid_track_pose_compose", "nid_track_pose_perturb", "nid_track_pose_to_Twc16",
+                  "nid_track_pose_from_Twc16",
+                  "nid_track_create", "nid_track_destroy", "nid_track_pyramid", "nid_track_set_lm", "nid_track_set_twists",
+                  "nid_track_set_pose", "nid_track_push_u16"]
+TRACK_FIRST, TRACK_OK, TRACK_LOST = 0, 1, 2
+
+
+class TrackResult(C.Structure):
+    """nid_track_result"""
+    _fields_ = [("pose7", C.c_double * 7), ("chi2", C.c_double), ("n_active", C.c_int32), ("best_origin", C.c_int32),
+                ("status", C.c_int32), ("promoted", C.c_int32), ("frame", C.c_int32), ("rounds", C.c_int32 * PYR_MAX_LEVELS)]
+
+
+assert C.sizeof(TrackResult) == 120
+
 _lib = None
 
 
@@ -175,6 +192,23 @@ def load():
         lib.nid_pyr_set_pair_u16.argtypes = [vp, u16p, C.c_double, c_u8p, c_u8p, c_dp]
         lib.nid_pyr_get_level_inputs.argtypes = [vp, C.c_int, u16p, c_u8p, c_u8p]
         lib.nid_pyr_multistart_lm.argtypes = [vp, c_dp, C.c_int, c_dp, C.c_int, C.c_double, c_ip, vp, c_ip, c_ip, c_ip, c_dp]
+    if hasattr(lib, "nid_track_create"):   # (likewise)
+        u16p = C.POINTER(C.c_uint16)
+        lib.nid_pyr_set_target_u8.argtypes = [vp, c_u8p]
+        lib.nid_pyr_promote_target_u16.argtypes = [vp, u16p, C.c_double, c_dp]
+        lib.nid_track_pose_inverse.argtypes = [c_dp, c_dp]
+        lib.nid_track_pose_compose.argtypes = [c_dp, c_dp, c_dp]
+        lib.nid_track_pose_perturb.argtypes = [c_dp, c_dp, c_dp]
+        lib.nid_track_pose_to_Twc16.argtypes = [c_dp, c_dp]
+        lib.nid_track_pose_from_Twc16.argtypes = [c_dp, c_dp]
+        lib.nid_track_create.argtypes = [C.POINTER(NidConfig), C.c_int, C.POINTER(vp)]
+        lib.nid_track_destroy.argtypes = [vp]
+        lib.nid_track_pyramid.restype = vp
+        lib.nid_track_pyramid.argtypes = [vp]
+        lib.nid_track_set_lm.argtypes = [vp, C.c_int, C.c_double, c_ip]
+        lib.nid_track_set_twists.argtypes = [vp, c_dp, C.c_int]
+        lib.nid_track_set_pose.argtypes = [vp, c_dp]
+        lib.nid_track_push_u16.argtypes = [vp, u16p, C.c_double, c_u8p, c_dp, C.POINTER(TrackResult)]
     _lib = lib
     return lib
 
@@ -617,7 +651,8 @@ class Pyramid:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.nid_pyr_destroy(self.h)
+            if not getattr(self, "_borrowed", False):   # (a Tracker's pyramid is the tracker's)
+                self.lib.nid_pyr_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -652,6 +687,20 @@ class Pyramid:
         assert d.size == N and a.size == N and b.size == N and T.size == 16
         self._check(self.lib.nid_pyr_set_pair_u16(self.h, d.ctypes.data_as(C.POINTER(C.c_uint16)), float(depth_factor),
                                                   a.ctypes.data_as(c_u8p), b.ctypes.data_as(c_u8p), _dp(T)), "nid_pyr_set_pair_u16")
+
+    def set_target(self, im1):
+        """nid_pyr_set_target_u8: a new target on every level; the reference side, its reference stage included, stays."""
+        b = _u8(im1).reshape(-1)
+        assert b.size == self.cfg0.rows * self.cfg0.cols
+        self._check(self.lib.nid_pyr_set_target_u8(self.h, b.ctypes.data_as(c_u8p)), "nid_pyr_set_target_u8")
+
+    def promote_target(self, depth_u16, depth_factor, T_wc_colmajor16):
+        """nid_pyr_promote_target_u16: the resident target becomes the reference, with its depth and camera-to-world matrix."""
+        d = np.ascontiguousarray(depth_u16, dtype=np.uint16).reshape(-1)
+        T = _d(T_wc_colmajor16)
+        assert d.size == self.cfg0.rows * self.cfg0.cols and T.size == 16
+        self._check(self.lib.nid_pyr_promote_target_u16(self.h, d.ctypes.data_as(C.POINTER(C.c_uint16)), float(depth_factor), _dp(T)),
+                    "nid_pyr_promote_target_u16")
 
     def get_level_inputs(self, level):
         """(depth_u16, im0, im1) of a level as the device holds them."""
@@ -692,6 +741,115 @@ def pyramid_from_pair(pair, bin_num, levels=3, device=0, depth_factor=1.0 / 5000
     pyr = Pyramid.create(pair, bin_num, levels=levels, device=device)
     pyr.set_pair_u16(pair.depth_u16, depth_factor, pair.im0, pair.im1, synth.matrix_colmajor16(pair.T_wc0))
     return pyr
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# include/nid/nid_pyr_stream.h: the pose arithmetic of a sequence (no device) and the tracker
+def _pose_call(name, out_len, *args):
+    lib = load()
+    a = [_d(x) for x in args]
+    out = np.zeros(out_len)
+    rc = getattr(lib, name)(*[_dp(x) for x in a], _dp(out))
+    if rc != NID_OK:
+        raise NidError(f"{name}: {lib.nid_status_string(rc).decode()} ({rc})")
+    return out
+
+
+def pose_inverse(pose7):
+    return _pose_call("nid_track_pose_inverse", 7, pose7)
+
+
+def pose_compose(a7, b7):
+    """a o b (b applied first), renormalised, w >= 0"""
+    return _pose_call("nid_track_pose_compose", 7, a7, b7)
+
+
+def pose_perturb(pose7, twist6):
+    """exp(twist) o pose, twist = (omega, upsilon): the LM chains' update"""
+    return _pose_call("nid_track_pose_perturb", 7, pose7, twist6)
+
+
+def pose_to_Twc16(pose7_cw):
+    """world -> camera pose7 -> column-major camera -> world matrix (what set_pair_u16 / promote_target take)"""
+    return _pose_call("nid_track_pose_to_Twc16", 16, pose7_cw)
+
+
+def pose_from_Twc16(T_wc_colmajor16):
+    return _pose_call("nid_track_pose_from_Twc16", 7, T_wc_colmajor16)
+
+
+class Tracker:
+    """A frame sequence on a resident pyramid of its own (nid_track): push() is the schedule of nid_pyr_stream.h."""
+
+    def __init__(self, rows, cols, cell_num, bin_num, fx, fy, cx, cy, levels=3, device=0):
+        self.lib = load()
+        self.cfg0 = NidConfig(rows, cols, cell_num, bin_num, 3, device, 0, 0, fx, fy, cx, cy)
+        h = C.c_void_p()
+        rc = self.lib.nid_track_create(C.byref(self.cfg0), int(levels), C.byref(h))
+        if rc != NID_OK:
+            raise NidError(f"nid_track_create: {self.lib.nid_status_string(rc).decode()} ({rc})")
+        self.h = h
+        # the tracker's pyramid as a Pyramid (not owned: closing it does nothing; it keeps this Tracker alive)
+        pyr = Pyramid.__new__(Pyramid)
+        pyr.lib, pyr.cfg0, pyr.bin_num = self.lib, self.cfg0, bin_num
+        pyr.h = C.c_void_p(self.lib.nid_track_pyramid(self.h))
+        pyr.levels = int(self.lib.nid_pyr_levels(pyr.h))
+        pyr._borrowed = True
+        pyr._owner = self
+        self.pyramid = pyr
+        self.levels = pyr.levels
+
+    @classmethod
+    def create(cls, pair, bin_num, levels=3, device=0):
+        return cls(pair.rows, pair.cols, pair.cell, bin_num, pair.fx, pair.fy, pair.cx, pair.cy, levels=levels, device=device)
+
+    def _check(self, rc, what):
+        if rc != NID_OK:
+            c0 = self.lib.nid_pyr_level(self.pyramid.h, 0) if self.h else None
+            msg = self.lib.nid_last_error(c0).decode() if c0 else ""
+            raise NidError(f"{what}: {self.lib.nid_status_string(rc).decode()} ({rc}) {msg}")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.pyramid.h = None
+            self.lib.nid_track_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_lm(self, iterations, delta, keep=None):
+        kp = None
+        if keep is not None:
+            kp = np.ascontiguousarray(keep, dtype=np.int32)
+            assert kp.size == self.levels, "keep: one entry per level"
+        self._check(self.lib.nid_track_set_lm(self.h, int(iterations), float(delta), _ip(kp)), "nid_track_set_lm")
+
+    def set_twists(self, twists6):
+        tw = _d(np.asarray(twists6, dtype=np.float64).reshape(-1, 6))
+        self._check(self.lib.nid_track_set_twists(self.h, _dp(tw) if tw.shape[0] else None, tw.shape[0]), "nid_track_set_twists")
+
+    def set_pose(self, pose7):
+        p = _d(pose7)
+        assert p.size == 7
+        self._check(self.lib.nid_track_set_pose(self.h, _dp(p)), "nid_track_set_pose")
+
+    def push(self, im, depth_u16=None, depth_factor=1.0 / 5000, T_wc_first=None):
+        """nid_track_push_u16: one frame.  Returns a dict of nid_track_result's members (pose7 and rounds as arrays)."""
+        N = self.cfg0.rows * self.cfg0.cols
+        a = _u8(im).reshape(-1)
+        d = np.ascontiguousarray(depth_u16, dtype=np.uint16).reshape(-1) if depth_u16 is not None else None
+        T = _d(T_wc_first) if T_wc_first is not None else None
+        assert a.size == N and (d is None or d.size == N) and (T is None or T.size == 16)
+        r = TrackResult()
+        self._check(self.lib.nid_track_push_u16(self.h, d.ctypes.data_as(C.POINTER(C.c_uint16)) if d is not None else None,
+                                                float(depth_factor), a.ctypes.data_as(c_u8p), _dp(T), C.byref(r)), "nid_track_push_u16")
+        return dict(pose7=np.array(r.pose7[:]), chi2=float(r.chi2), n_active=int(r.n_active), best_origin=int(r.best_origin),
+                    status=int(r.status), promoted=int(r.promoted), frame=int(r.frame),
+                    rounds=np.array(r.rounds[:self.levels], dtype=np.int32))
 
 
 # ---------------------------------------------------------------------------------------------------------------

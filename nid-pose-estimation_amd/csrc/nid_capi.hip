@@ -23,11 +23,13 @@
 #include "nid/nid_c.h"
 #include "nid/nid_multistart.h"
 #include "nid/nid_pyr.h"
+#include "nid/nid_pyr_stream.h"
 #include "nid_eval_launch.h"
 #include "nid_pose_pool.h"             // pose_sizes, seq_fusion: per-pose buffer sizes and the fused grids' budget rule (no HIP in it)
 #include "nid_direct_sum.h"            // DirectSum, add_block: the host's arithmetic and order of a DIRECT / GROUP-DIRECT launch (no HIP in it)
 #include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
-#include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_pyr_down, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
+#include "nid_track_pose.h"            // pose inverse / compose / perturb of nid_pyr_stream.h, on nid_lm_step.h's SE(3) text (no HIP in it)
+#include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_pyr_down (+ _u8, _depth), k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
 
 using namespace nid;
@@ -1077,9 +1079,8 @@ PairStage pair_stage_layout(const Geometry &g) {
   return L;
 }
 
-// pair_u16_enqueue in two parts (nid_pyr.inc runs the second for every pyramid level, the first for level 0 only).
-// UPLOAD: the pair through the context's pinned block onto `st` -- depth16_dev, im0_dev, im1_dev, Twc_dev.
-int pair_u16_upload(nid_ctx *ctx, const uint16_t *depth_u16, const uint8_t *im0, const uint8_t *im1, const double *Twc, hipStream_t stream) {
+// depth16_dev and the pinned block, created on first use (pair_u16_upload; nid_pyr_stream.inc's calls, which may come first)
+int pair_stage_ensure(nid_ctx *ctx) {
   const Geometry &g = ctx->g;
   const size_t N = (size_t)g.rows * g.cols;
   const PairStage L = pair_stage_layout(g);
@@ -1087,6 +1088,17 @@ int pair_u16_upload(nid_ctx *ctx, const uint16_t *depth_u16, const uint8_t *im0,
   if (!ctx->pair_stage && hipHostMalloc(reinterpret_cast<void **>(&ctx->pair_stage), L.bytes, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError(); ctx->pair_stage = nullptr; return NID_ERR_NOMEM;
   }
+  return NID_OK;
+}
+
+// pair_u16_enqueue in two parts (nid_pyr.inc runs the second for every pyramid level, the first for level 0 only).
+// UPLOAD: the pair through the context's pinned block onto `st` -- depth16_dev, im0_dev, im1_dev, Twc_dev.
+int pair_u16_upload(nid_ctx *ctx, const uint16_t *depth_u16, const uint8_t *im0, const uint8_t *im1, const double *Twc, hipStream_t stream) {
+  const Geometry &g = ctx->g;
+  const size_t N = (size_t)g.rows * g.cols;
+  const PairStage L = pair_stage_layout(g);
+  const int rc = pair_stage_ensure(ctx);
+  if (rc) return rc;
   uint8_t *st = ctx->pair_stage;
   std::memcpy(st + L.depth, depth_u16, 2 * N);
   std::memcpy(st + L.im0, im0, N);
@@ -1099,18 +1111,28 @@ int pair_u16_upload(nid_ctx *ctx, const uint16_t *depth_u16, const uint8_t *im0,
   return NID_OK;
 }
 
-// DEVICE: from depth16_dev, im0_dev, im1_dev and Twc_dev on `stream`: depth -> metres, back-projection + tiling, the
-// target's margins.  Launches only: the caller asks hipGetLastError behind its last launch.
-void pair_u16_device(nid_ctx *ctx, double depth_factor, hipStream_t stream) {
+// DEVICE: from depth16_dev, im0_dev, im1_dev and Twc_dev on `stream`: depth -> metres, back-projection + tiling (the
+// REFERENCE half), the target's margins (the TARGET half; nid_pyr_stream.inc runs either alone).  Launches only: the
+// caller asks hipGetLastError behind its last launch.
+void pair_u16_device_ref(nid_ctx *ctx, double depth_factor, hipStream_t stream) {
   const Geometry &g = ctx->g;
   const size_t N = (size_t)g.rows * g.cols;
   hipLaunchKernelGGL(k_depth_u16, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (long)N, ctx->depth16_dev, depth_factor, ctx->depth_dev);
   const long total = (long)g.nloc * g.pstride;
   hipLaunchKernelGGL(k_tile, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, g, ctx->depth_dev,
                      (const double *)nullptr, ctx->im0_dev, ctx->Twc_dev, ctx->t, (double *)nullptr);
+}
+
+void pair_u16_device_target(nid_ctx *ctx, hipStream_t stream) {
+  const Geometry &g = ctx->g;
   const long mtotal = (long)(g.rows + 1) * (g.cols + 1);
   hipLaunchKernelGGL(k_im1_margins, dim3((unsigned)((mtotal + 255) / 256)), dim3(256), 0, stream, g.rows, g.cols,
                      ctx->im1_stride, ctx->im1_dev, ctx->im1s_dev);
+}
+
+void pair_u16_device(nid_ctx *ctx, double depth_factor, hipStream_t stream) {
+  pair_u16_device_ref(ctx, depth_factor, stream);
+  pair_u16_device_target(ctx, stream);
 }
 
 int pair_u16_enqueue(nid_ctx *ctx, const uint16_t *depth_u16, double depth_factor, const uint8_t *im0, const uint8_t *im1,
@@ -2203,3 +2225,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- a device-built resident pyramid and coarse-to-fine multi-start LM on it (include/nid/nid_pyr.h) ---
 #include "nid_pyr.inc"
+
+// ---- frame streams on the resident pyramid: a new target alone, target -> reference, a tracker (include/nid/nid_pyr_stream.h) ---
+#include "nid_pyr_stream.inc"

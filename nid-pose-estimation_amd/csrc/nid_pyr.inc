@@ -13,7 +13,7 @@ struct nid_pyr {
   int levels = 0;
   nid_ctx *ctx[NID_PYR_MAX_LEVELS] = {};
   hipEvent_t idle[NID_PYR_MAX_LEVELS][2] = {};  // a level's stream / aux_stream have reached this call
-  bool have_pair = false;
+  bool have_pair = false;  // a reference is resident on every level (nid_pyr_set_pair_u16, or a promoted target: nid_pyr_stream.inc)
 };
 
 namespace {
@@ -21,6 +21,54 @@ namespace {
 int pyr_fail(nid_pyr *p, int rc, const std::string &why) {
   p->ctx[0]->last_error = why;
   return rc;
+}
+
+// The opening of every call that rewrites the levels' inputs (nid_pyr_set_pair_u16; nid_pyr_stream.inc's two), in two
+// steps with the caller's clearing of the ready flags between them.  REFUSE: NID_ERR_STATE while a level has an
+// uncollected launch.
+int pyr_refuse_pending(nid_pyr *p, const char *what) {
+  for (int l = 0; l < p->levels; l++)
+    if (any_pending(p->ctx[l])) return pyr_fail(p, NID_ERR_STATE, std::string(what) + ": a launch is pending on level " + std::to_string(l) + ": nid_wait() it first");
+  return NID_OK;
+}
+
+// FRONT: the device selected, resident evaluators retired, and what the levels' own streams still run -- it reads the
+// buffers the call rewrites -- put in front of level 0's stream, on the device, with one event per stream.
+int pyr_front(nid_pyr *p) {
+  nid_ctx *c0 = p->ctx[0];
+  NID_HIP(c0, hipSetDevice(c0->cfg.device));
+  for (int l = 0; l < p->levels; l++) resident_retire(p->ctx[l]);
+  const hipStream_t st = c0->stream;
+  for (int l = 0; l < p->levels; l++) {
+    nid_ctx *ctx = p->ctx[l];
+    const hipStream_t own[2] = {ctx->stream, ctx->aux_stream};
+    for (int s = 0; s < 2; s++) {
+      if (!own[s] || own[s] == st) continue;
+      NID_HIP(c0, hipEventRecord(p->idle[l][s], own[s]));
+      NID_HIP(c0, hipStreamWaitEvent(st, p->idle[l][s], 0));
+    }
+  }
+  return NID_OK;
+}
+
+// The close: hipGetLastError behind the last launch, ONE synchronisation; an error drains the stream (nothing of the call
+// stays in flight).  The caller marks the levels ready after NID_OK.
+int pyr_drain(nid_pyr *p, int rc) {
+  (void)hipStreamSynchronize(p->ctx[0]->stream);
+  return rc;
+}
+
+int pyr_finish(nid_pyr *p, const char *what) {
+  nid_ctx *c0 = p->ctx[0];
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, std::string(what) + ": a launch failed: " + hipGetErrorString(e)));
+  NID_HIP(c0, hipStreamSynchronize(c0->stream));
+  return NID_OK;
+}
+
+unsigned pyr_down_blocks(const nid_ctx *dst) {
+  const long threads = (long)dst->g.rows * ((dst->g.cols + kPyrRun - 1) / kPyrRun);
+  return (unsigned)((threads + 255) / 256);
 }
 
 }  // namespace
@@ -84,44 +132,25 @@ nid_ctx *nid_pyr_level(nid_pyr *p, int level) { return (p && level >= 0 && level
 int nid_pyr_set_pair_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, const uint8_t *im0, const uint8_t *im1,
                          const double *Twc) {
   if (!p || !depth_u16 || !im0 || !im1 || !Twc) return NID_ERR_INVALID_ARG;
-  for (int l = 0; l < p->levels; l++)
-    if (any_pending(p->ctx[l])) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_set_pair_u16: a launch is pending on level " + std::to_string(l) + ": nid_wait() it first");
+  int rc = pyr_refuse_pending(p, "nid_pyr_set_pair_u16");
+  if (rc) return rc;
   // from here on the levels are being overwritten: none of them is ready until the stream has drained
   p->have_pair = false;
   for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_target = p->ctx[l]->have_href = false;
+  if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
-  NID_HIP(c0, hipSetDevice(c0->cfg.device));
-  for (int l = 0; l < p->levels; l++) resident_retire(p->ctx[l]);
   const hipStream_t st = c0->stream;
-  // what the levels' own streams still run reads the buffers this call rewrites: in front of it, on the device
-  for (int l = 0; l < p->levels; l++) {
-    nid_ctx *ctx = p->ctx[l];
-    const hipStream_t own[2] = {ctx->stream, ctx->aux_stream};
-    for (int s = 0; s < 2; s++) {
-      if (!own[s] || own[s] == st) continue;
-      NID_HIP(c0, hipEventRecord(p->idle[l][s], own[s]));
-      NID_HIP(c0, hipStreamWaitEvent(st, p->idle[l][s], 0));
-    }
-  }
-  auto drain = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };  // (an error leaves nothing of this call in flight)
-  int rc = pair_u16_upload(c0, depth_u16, im0, im1, Twc, st);
-  if (rc) return drain(rc);
+  if ((rc = pair_u16_upload(c0, depth_u16, im0, im1, Twc, st))) return pyr_drain(p, rc);
   const PairStage L0 = pair_stage_layout(c0->g);
   for (int l = 1; l < p->levels; l++) {
     nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
     if (hipMemcpyAsync(dst->Twc_dev, c0->pair_stage + L0.twc, 16 * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)
-      return drain(pyr_fail(p, NID_ERR_HIP, "nid_pyr_set_pair_u16: hipMemcpyAsync(T_wc0)"));
-    const int rows2 = dst->g.rows, cols2 = dst->g.cols;
-    const long threads = (long)rows2 * ((cols2 + kPyrRun - 1) / kPyrRun);
-    hipLaunchKernelGGL(k_pyr_down, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, rows2, cols2, src->im0_dev, src->im1_dev,
+      return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, "nid_pyr_set_pair_u16: hipMemcpyAsync(T_wc0)"));
+    hipLaunchKernelGGL(k_pyr_down, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->im0_dev, src->im1_dev,
                        src->depth16_dev, depth_factor, dst->im0_dev, dst->im1_dev, dst->depth16_dev);
   }
   for (int l = 0; l < p->levels; l++) pair_u16_device(p->ctx[l], depth_factor, st);
-  {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return drain(pyr_fail(p, NID_ERR_HIP, std::string("nid_pyr_set_pair_u16: a launch failed: ") + hipGetErrorString(e)));
-  }
-  NID_HIP(c0, hipStreamSynchronize(st));
+  if ((rc = pyr_finish(p, "nid_pyr_set_pair_u16"))) return rc;
   for (int l = 0; l < p->levels; l++) {
     nid_ctx *ctx = p->ctx[l];
     ctx->have_ref = ctx->have_target = true;  // (have_href stays false: the reference stage is the caller's)

@@ -1,6 +1,6 @@
 // nid_setup_kernels.hip.h -- the once-per-pair kernels: back-projection + tiling, the target image's margins, the reference
 // stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
-// next pyramid level (k_pyr_down).
+// next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
@@ -105,6 +105,21 @@ __device__ inline uint16_t pyr_depth_mean(const uint16_t v[4], double factor) {
   return n ? (uint16_t)((2 * sum + n) / (2 * n)) : (uint16_t)0;
 }
 
+// kPyrRun image pixels of one plane: 8 bytes of each of the two source rows a and b -> 4 packed output bytes
+__device__ inline unsigned pyr_box4(const uint8_t *a, const uint8_t *b) {
+  unsigned long long ra, rb;
+  __builtin_memcpy(&ra, a, 8);
+  __builtin_memcpy(&rb, b, 8);
+  unsigned o = 0;
+#pragma unroll
+  for (int k = 0; k < kPyrRun; k++) {
+    const unsigned s = (unsigned)((ra >> (16 * k)) & 0xff) + (unsigned)((ra >> (16 * k + 8)) & 0xff) +
+                       (unsigned)((rb >> (16 * k)) & 0xff) + (unsigned)((rb >> (16 * k + 8)) & 0xff);
+    o |= ((s + 2) >> 2) << (8 * k);
+  }
+  return o;
+}
+
 __global__ void __launch_bounds__(256) k_pyr_down(int rows2, int cols2, const uint8_t *__restrict__ im0, const uint8_t *__restrict__ im1,
                                                   const uint16_t *__restrict__ depth, double factor, uint8_t *__restrict__ o_im0,
                                                   uint8_t *__restrict__ o_im1, uint16_t *__restrict__ o_depth) {
@@ -116,20 +131,7 @@ __global__ void __launch_bounds__(256) k_pyr_down(int rows2, int cols2, const ui
   const size_t top = (size_t)(2 * r) * cols + 2 * (size_t)c0;  // source: rows 2r and 2r + 1, from column 2 c0
   const size_t out = (size_t)r * cols2 + c0;
   if (c0 + kPyrRun <= cols2) {
-    auto box4 = [](const uint8_t *a, const uint8_t *b) {
-      unsigned long long ra, rb;
-      __builtin_memcpy(&ra, a, 8);
-      __builtin_memcpy(&rb, b, 8);
-      unsigned o = 0;
-#pragma unroll
-      for (int k = 0; k < kPyrRun; k++) {
-        const unsigned s = (unsigned)((ra >> (16 * k)) & 0xff) + (unsigned)((ra >> (16 * k + 8)) & 0xff) +
-                           (unsigned)((rb >> (16 * k)) & 0xff) + (unsigned)((rb >> (16 * k + 8)) & 0xff);
-        o |= ((s + 2) >> 2) << (8 * k);
-      }
-      return o;
-    };
-    const unsigned p0 = box4(im0 + top, im0 + top + cols), p1 = box4(im1 + top, im1 + top + cols);
+    const unsigned p0 = pyr_box4(im0 + top, im0 + top + cols), p1 = pyr_box4(im1 + top, im1 + top + cols);
     __builtin_memcpy(o_im0 + out, &p0, 4);
     __builtin_memcpy(o_im1 + out, &p1, 4);
     uint16_t da[2 * kPyrRun], db[2 * kPyrRun], od[kPyrRun];
@@ -146,6 +148,55 @@ __global__ void __launch_bounds__(256) k_pyr_down(int rows2, int cols2, const ui
       const size_t s = top + 2 * (size_t)k;
       o_im0[out + k] = (uint8_t)((im0[s] + im0[s + 1] + im0[s + cols] + im0[s + cols + 1] + 2) >> 2);
       o_im1[out + k] = (uint8_t)((im1[s] + im1[s + 1] + im1[s + cols] + im1[s + cols + 1] + 2) >> 2);
+      const uint16_t v[4] = {depth[s], depth[s + 1], depth[s + cols], depth[s + cols + 1]};
+      o_depth[out + k] = pyr_depth_mean(v, factor);
+    }
+  }
+}
+
+// The one-plane forms of k_pyr_down (nid_pyr_stream.h: a new target alone, a new reference's depth alone): the same thread
+// map, arithmetic and access form, plane for plane.  The source is (2 rows2) x (2 cols2).
+__global__ void __launch_bounds__(256) k_pyr_down_u8(int rows2, int cols2, const uint8_t *__restrict__ src, uint8_t *__restrict__ dst) {
+  const int runs = (cols2 + kPyrRun - 1) / kPyrRun;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)rows2 * runs) return;
+  const int r = (int)(gid / runs), c0 = (int)(gid % runs) * kPyrRun;
+  const size_t cols = 2 * (size_t)cols2;
+  const size_t top = (size_t)(2 * r) * cols + 2 * (size_t)c0;
+  const size_t out = (size_t)r * cols2 + c0;
+  if (c0 + kPyrRun <= cols2) {
+    const unsigned p = pyr_box4(src + top, src + top + cols);
+    __builtin_memcpy(dst + out, &p, 4);
+  } else {
+    for (int k = 0; c0 + k < cols2; k++) {
+      const size_t s = top + 2 * (size_t)k;
+      dst[out + k] = (uint8_t)((src[s] + src[s + 1] + src[s + cols] + src[s + cols + 1] + 2) >> 2);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_pyr_down_depth(int rows2, int cols2, const uint16_t *__restrict__ depth, double factor,
+                                                        uint16_t *__restrict__ o_depth) {
+  const int runs = (cols2 + kPyrRun - 1) / kPyrRun;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid >= (long)rows2 * runs) return;
+  const int r = (int)(gid / runs), c0 = (int)(gid % runs) * kPyrRun;
+  const size_t cols = 2 * (size_t)cols2;
+  const size_t top = (size_t)(2 * r) * cols + 2 * (size_t)c0;
+  const size_t out = (size_t)r * cols2 + c0;
+  if (c0 + kPyrRun <= cols2) {
+    uint16_t da[2 * kPyrRun], db[2 * kPyrRun], od[kPyrRun];
+    __builtin_memcpy(da, depth + top, sizeof(da));
+    __builtin_memcpy(db, depth + top + cols, sizeof(db));
+#pragma unroll
+    for (int k = 0; k < kPyrRun; k++) {
+      const uint16_t v[4] = {da[2 * k], da[2 * k + 1], db[2 * k], db[2 * k + 1]};
+      od[k] = pyr_depth_mean(v, factor);
+    }
+    __builtin_memcpy(o_depth + out, od, sizeof(od));
+  } else {
+    for (int k = 0; c0 + k < cols2; k++) {
+      const size_t s = top + 2 * (size_t)k;
       const uint16_t v[4] = {depth[s], depth[s + 1], depth[s + cols], depth[s + cols + 1]};
       o_depth[out + k] = pyr_depth_mean(v, factor);
     }
