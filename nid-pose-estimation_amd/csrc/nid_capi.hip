@@ -25,6 +25,7 @@
 #include "nid/nid_pyr.h"
 #include "nid/nid_pyr_stream.h"
 #include "nid_eval_launch.h"
+#include "nid_hip_owned.h"            // DevBuf, PinnedBuf, Event, Stream: who owns the device memory, pinned memory, events and streams (no kernels in it)
 #include "nid_pose_pool.h"             // pose_sizes, seq_fusion: per-pose buffer sizes and the fused grids' budget rule (no HIP in it)
 #include "nid_direct_sum.h"            // DirectSum, add_block: the host's arithmetic and order of a DIRECT / GROUP-DIRECT launch (no HIP in it)
 #include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
@@ -53,14 +54,11 @@ enum class Delivery : unsigned char {
 struct Slot {
   double *cellout_dev = nullptr;
   double *reduced_dev = nullptr;   // device scratch target (evaluate path / slot_buffers)
-  double *cellout_host = nullptr;  // pinned, mapped: the blocking per-cell calls let the kernel write here directly
-  double *cellout_host_devptr = nullptr;
+  PinnedBuf<double> cellout_host;  // pinned, mapped: the blocking per-cell calls let the kernel write here directly
   double *reduced_host = nullptr;  // pinned, mapped: [32 doubles][u64 sequence word]
   double *reduced_host_devptr = nullptr;
-  double *quad_host = nullptr;     // pinned, mapped, created on first use: [nloc][kDirectRec] per-cell records of a DIRECT launch (wait_direct)
-  double *quad_host_devptr = nullptr;
-  double *groups_host = nullptr;   // pinned, mapped, created on first use: [ngroups][32] group sums of a GROUP-DIRECT launch (wait_groups)
-  double *groups_host_devptr = nullptr;
+  PinnedBuf<double> quad_host;     // pinned, mapped, created on first use: [nloc][kDirectRec] per-cell records of a DIRECT launch (wait_direct)
+  PinnedBuf<double> groups_host;   // pinned, mapped, created on first use: [ngroups][32] group sums of a GROUP-DIRECT launch (wait_groups)
   Delivery delivery = Delivery::SeqWord;  // the route home of the launch in flight (meaningful while `pending`, and inside a blocking call)
   // properties of the BUFFERS, whatever the route: a launch wrote (or may still write) into quad_host / groups_host and
   // no wait has consumed it
@@ -68,7 +66,7 @@ struct Slot {
   bool direct_jac = false;         // the DIRECT launch or resident request in flight carries Jacobians
   double direct_delta = 0.0;       // ... its Huber delta
   unsigned long long seq = 0;      // sequence number of the last launch into this slot
-  hipEvent_t done = nullptr, e0 = nullptr, e1 = nullptr;  // e0 / e1: timing events, created on first use
+  Event done, e0, e1;              // e0 / e1: timing events, created on first use
   bool pending = false;
   bool timed = false;
   int done_slot = 0;               // Delivery::Event: the slot whose `done` event covers this one's launch
@@ -78,12 +76,13 @@ inline bool is_resident(const Slot &S) { return S.delivery == Delivery::Resident
 // What every pose of a grid needs for itself: per-cell blocks, group sums, tickets (zero between launches: the kernels
 // leave them so) and -- for a private grid -- its argument record (pinned mirror + device array).  The public slots are
 // carved from one (no records); nid_run_sequence's fused grids and nid_multistart_lm each own one.  A private grid of
-// poses is run with pool_ensure, pool_record + the pose per record, and launch_records; pool_free with the context.
+// poses is run with pool_ensure, pool_record + the pose per record, and launch_records.
 struct PosePool {
   size_t poses = 0;
-  double *quad = nullptr, *gpart = nullptr;          // [poses][nloc * kQuad], [poses][ngroups * kQuad]
-  unsigned *ticket = nullptr;                        // [poses][ticket words]
-  SlotArgs *rec_dev = nullptr, *rec_host = nullptr;  // [poses], or null
+  DevBuf<double> quad, gpart;   // [poses][nloc * kQuad], [poses][ngroups * kQuad]
+  DevBuf<unsigned> ticket;      // [poses][ticket words]
+  DevBuf<SlotArgs> rec_dev;     // [poses], or empty
+  PinnedBuf<SlotArgs> rec_host;
 };
 static_assert(sizeof(SlotArgs) == 224, "the budget rule's table (tests/cpp/pose_pool_check.cpp) assumes this record");
 static_assert(kPoseBlock == kQuad && kPoseBlock == kReducedLen && kSeqGridLimit == kSeqGridMax, "nid_pose_pool.h restates these");
@@ -92,6 +91,14 @@ static_assert(kSumBlock == kQuad && kSumBlock == kReducedLen, "nid_direct_sum.h 
 }  // namespace
 
 struct nid_ctx {
+  // The streams FIRST: `delete ctx` releases the members in reverse order, so every buffer and event below goes before them.
+  // own_stream: setup + blocking calls; aux_stream: odd slots of the pipelined path, so that
+  // launch N+1 overlaps the reduction tail and the launch gap of launch N (separate
+  // per-slot buffers make that safe).  An external stream (nid_set_stream: borrowed) disables it.
+  // copy_stream: nid_run_sequence's result copies (ensure_seq_ring).  stream: the current one, own_stream or the borrowed one.
+  Stream own_stream, aux_stream, copy_stream;
+  hipStream_t stream = nullptr;
+  bool external_stream = false;
   nid_config cfg{};
   Geometry g{};
   int jac_bound = NID_JACBOUND_CPU;
@@ -108,11 +115,11 @@ struct nid_ctx {
     bool running = false;          // the kernel is on the device
     int probed = 0;                // 0: not yet, 1: the mailbox is CPU-addressable, -1: it is not (resident launches unavailable)
     int nt = 0;                    // workgroup shape of the running kernel
-    ResidentCtl *ctl = nullptr;    // fine-grained device memory, written by the CPU through the PCIe BAR
-    hipStream_t stream = nullptr;
+    ResidentCtl *ctl = nullptr;    // fine-grained device memory (hipExtMallocWithFlags), written by the CPU through the PCIe BAR; freed by nid_destroy
+    Stream stream;
     unsigned long long seq = 0;
     std::chrono::steady_clock::time_point last_post{};
-    double *rec_host = nullptr, *rec_devptr = nullptr;  // [nloc][kDirectRec], pinned + mapped
+    PinnedBuf<double> rec_host;    // [nloc][kDirectRec], pinned + mapped
     int pending_slot = -1;         // the slot whose request is in flight (one at a time)
     // the request in flight, for the fallback (a kernel that had left: re-issued as an ordinary DIRECT launch)
     Pose pose{};
@@ -123,37 +130,35 @@ struct nid_ctx {
     int unfit_nt = 0;              // the launch shape a start was refused for (its workgroups do not all fit the device)
   } res;
   std::vector<double> direct_rho1;  // wait_direct: the cells' Huber weights between its two passes
-  // own_stream: setup + blocking calls; aux_stream: odd slots of the pipelined path, so that
-  // launch N+1 overlaps the reduction tail and the launch gap of launch N (separate
-  // per-slot buffers make that safe).  An external stream (nid_set_stream) disables it.
-  hipStream_t own_stream = nullptr, aux_stream = nullptr, stream = nullptr;
-  bool external_stream = false;
-  Tiles t{};
+  Tiles t{};  // (views of `tiles`)
+  struct TileBufs { DevBuf<double> X, Y, Z, W; DevBuf<int8_t> JR; DevBuf<uint8_t> I0; } tiles;
   // launches of more than kMaxBatch poses: per-pose argument records travel through a small ring of device
   // arrays (host fills the pinned mirror, one in-stream copy, then the kernel)
   static constexpr int kExtRing = 4;
-  SlotArgs *ext_dev[kExtRing] = {nullptr, nullptr, nullptr, nullptr};
-  SlotArgs *ext_host[kExtRing] = {nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ext_done[kExtRing] = {nullptr, nullptr, nullptr, nullptr};
+  DevBuf<SlotArgs> ext_dev[kExtRing];
+  PinnedBuf<SlotArgs> ext_host[kExtRing];
+  Event ext_done[kExtRing];
   bool ext_busy[kExtRing] = {false, false, false, false};
   int ext_next = 0;
-  uint8_t *im1_dev = nullptr, *im0_dev = nullptr;
-  int16_t *im1s_dev = nullptr;   // int16 copy with the extrapolated top / left margin the evaluation kernel samples (k_im1_margins)
+  DevBuf<uint8_t> im1_dev, im0_dev;
+  DevBuf<int16_t> im1s_dev;   // int16 copy with the extrapolated top / left margin the evaluation kernel samples (k_im1_margins)
   int im1_stride = 0;
-  double *depth_dev = nullptr, *points_dev = nullptr, *Twc_dev = nullptr;
-  uint16_t *depth16_dev = nullptr;   // nid_set_pair_u16: the depth map as uploaded, and the pinned block its inputs and
-  uint8_t *pair_stage = nullptr;     // per-cell outputs travel through (created on first use)
-  int *Nc_dev = nullptr;
-  double *Href_dev = nullptr;
-  double *dbg_u = nullptr, *dbg_v = nullptr, *dbg_ic = nullptr, *dbg_wc = nullptr;
-  int *dbg_jc = nullptr;
-  long long *dbg_stamps = nullptr;
+  DevBuf<double> depth_dev, points_dev, Twc_dev;
+  DevBuf<uint16_t> depth16_dev;   // nid_set_pair_u16: the depth map as uploaded, and the pinned block its inputs and
+  PinnedBuf<uint8_t> pair_stage;  // per-cell outputs travel through (created on first use)
+  DevBuf<int> Nc_dev;
+  DevBuf<double> Href_dev;
+  DevBuf<double> dbg_u, dbg_v, dbg_ic, dbg_wc;
+  DevBuf<int> dbg_jc;
+  DevBuf<long long> dbg_stamps;
   // compute_href's per-pixel outputs in image order (k_untile_bs) and their pinned staging, created on first use
-  double *bsv_img_dev = nullptr, *bsv_stage = nullptr;
-  int *bsi_img_dev = nullptr, *bsi_stage = nullptr;
-  hipEvent_t bs_part_done[4] = {nullptr, nullptr, nullptr, nullptr};  // (kBsParts)
-  unsigned long long *repair_count_dev = nullptr;  // EvalParams::repair_count (nid_debug_repair_count)
-  unsigned *repair_queue_dev[2] = {nullptr, nullptr};  // EvalParams::repair_queue of launches on `stream` / on aux_stream (k_repair)
+  DevBuf<double> bsv_img_dev;
+  PinnedBuf<double> bsv_stage;
+  DevBuf<int> bsi_img_dev;
+  PinnedBuf<int> bsi_stage;
+  Event bs_part_done[4];  // (kBsParts)
+  DevBuf<unsigned long long> repair_count_dev;  // EvalParams::repair_count (nid_debug_repair_count)
+  DevBuf<unsigned> repair_queue_dev[2];  // EvalParams::repair_queue of launches on `stream` / on aux_stream (k_repair)
   bool dbg_enabled = false;
   int dbg_jac = 0;
   bool timing = false;
@@ -161,14 +166,14 @@ struct nid_ctx {
   double hist_scale = 0, hist_inv_scale = 0;            // k_href: whole-cell sums below 2^62
   int group_size = 1, ngroups = 1;
   int math_mode = NID_MATH_FAST;
-  double *ctab_dev = nullptr;
+  DevBuf<double> ctab_dev;
   Slot slots[NID_SLOTS];
-  // nid_run_sequence: result buffers of the launches in flight (device + pinned host), their copy stream and events
+  // nid_run_sequence: result buffers of the launches in flight (device + pinned host) and their events; every entry of
+  // the two rings holds at least the largest batch asked for so far (ensure_seq_ring)
   static constexpr int kSeqRing = 16;  // launches in flight: min(kSeqRing, NID_SLOTS / batch)
-  double *seq_dev[kSeqRing] = {}, *seq_host[kSeqRing] = {};
-  hipEvent_t seq_done[kSeqRing] = {}, seq_fence[kSeqRing] = {};
-  size_t seq_cap = 0;
-  hipStream_t copy_stream = nullptr;
+  DevBuf<double> seq_dev[kSeqRing];
+  PinnedBuf<double> seq_host[kSeqRing];
+  Event seq_done[kSeqRing], seq_fence[kSeqRing];
   // nid_run_sequence's FUSED grids (several consecutive batches of a long sequence in one grid of up to kSeqGridMax poses):
   // a PosePool of grid x depth poses, entry r of it beside the result blocks in seq_dev[r] / seq_host[r].  Private to the
   // pipeline: the public slots are neither used nor marked pending by a fused sequence.  Made on first use (ensure_seq_pool).
@@ -181,16 +186,18 @@ struct nid_ctx {
   struct MsPool {
     int chains = 0, rounds = 0;
     PosePool poses;
-    double *reduced = nullptr;
-    unsigned *running_dev = nullptr, *running_host = nullptr;  // (running_host: pinned)
-    nid_ms_state *state_dev = nullptr, *state_host = nullptr;  // (state_host: pinned, [chains])
-    nid_ms_trace *trace_dev = nullptr;
-    size_t trace_cap = 0;
+    DevBuf<double> reduced;
+    DevBuf<unsigned> running_dev;
+    PinnedBuf<unsigned> running_host;
+    DevBuf<nid_ms_state> state_dev;
+    PinnedBuf<nid_ms_state> state_host;  // [chains]
+    DevBuf<nid_ms_trace> trace_dev;
   } ms;
   // what the slots' buffers are carved from (one allocation per kind; quad, gpart and tickets: slot_pool, without records)
   PoseSizes sz{};  // per-pose sizes of this geometry (nid_pose_pool.h)
   PosePool slot_pool;
-  double *slab_cellout = nullptr, *slab_reduced = nullptr, *slab_reduced_host = nullptr;
+  DevBuf<double> slab_cellout, slab_reduced;
+  PinnedBuf<double> slab_reduced_host;
   std::string last_error;
 };
 
@@ -200,22 +207,16 @@ void resident_retire(nid_ctx *ctx);  // every call that changes what a resident 
 int launch_batch(nid_ctx *ctx, int first_slot, int n, const Pose *poses, int want_jac, double delta, double *reduced_dev_base = nullptr,
                  bool on_aux_stream = false, bool relaunch_ok = false, bool allow_direct = true);
 int resident_quiesce(nid_ctx *ctx);  // ... and every ordinary evaluation launch (the resident workgroups hold most of every CU)
-void free_ms_pool(nid_ctx *ctx);
 
+// (an owner's alloc / grow / create goes through it like any other call: NID_HIP(ctx, ctx->points_dev.alloc(n)))
 #define NID_HIP(ctx, expr)                                                            \
   do {                                                                                \
     hipError_t _e = (expr);                                                           \
     if (_e != hipSuccess) {                                                           \
       (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);          \
-      return NID_ERR_HIP;                                                             \
+      return _e == hipErrorOutOfMemory ? NID_ERR_NOMEM : NID_ERR_HIP;                 \
     }                                                                                 \
   } while (0)
-
-template <typename T>
-int dev_alloc(nid_ctx *ctx, T **p, size_t n) {
-  NID_HIP(ctx, hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T)));
-  return NID_OK;
-}
 
 void pose_from_pose7(const double *p, int mode, Pose *out) {
   // to_homogeneous_matrix (se3quat.h:270-278) = Eigen toRotationMatrix
@@ -427,25 +428,19 @@ void fill_common_params(nid_ctx *ctx, double delta, EvalParams *P) {
 }
 
 // ---- per-pose buffers and records: PosePool ----------------------------------------------------------------------
-void pool_free(PosePool &Q) {
-  (void)hipFree(Q.quad); (void)hipFree(Q.gpart); (void)hipFree(Q.ticket); (void)hipFree(Q.rec_dev);
-  if (Q.rec_host) (void)hipHostFree(Q.rec_host);
-  Q = PosePool();
-}
-
-// the pool for exactly `poses` poses (a context's geometry is fixed: only their number changes between calls)
+// the pool for exactly `poses` poses (a context's geometry is fixed: only their number changes between calls); a step
+// that fails leaves a pool of no poses, which the next call makes anew
 int pool_ensure(nid_ctx *ctx, PosePool &Q, size_t poses, bool with_records) {
   if (Q.poses == poses) return NID_OK;
   resident_retire(ctx);  // (hipFree waits for the whole device)
-  pool_free(Q);
-  int rc;
-  if ((rc = dev_alloc(ctx, &Q.quad, poses * ctx->sz.quad))) return rc;
-  if ((rc = dev_alloc(ctx, &Q.gpart, poses * ctx->sz.gpart))) return rc;
-  if ((rc = dev_alloc(ctx, &Q.ticket, poses * ctx->sz.ticket))) return rc;
+  Q = PosePool();
+  NID_HIP(ctx, Q.quad.alloc(poses * ctx->sz.quad));
+  NID_HIP(ctx, Q.gpart.alloc(poses * ctx->sz.gpart));
+  NID_HIP(ctx, Q.ticket.alloc(poses * ctx->sz.ticket));
   NID_HIP(ctx, hipMemset(Q.ticket, 0, poses * ctx->sz.ticket * sizeof(unsigned)));  // (the kernels leave them zero behind every launch)
   if (with_records) {
-    if ((rc = dev_alloc(ctx, &Q.rec_dev, poses))) return rc;
-    if (hipHostMalloc(reinterpret_cast<void **>(&Q.rec_host), poses * sizeof(SlotArgs), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
+    NID_HIP(ctx, Q.rec_dev.alloc(poses));
+    NID_HIP(ctx, Q.rec_host.alloc(poses));
   }
   Q.poses = poses;
   return NID_OK;
@@ -511,24 +506,20 @@ int refuse_pending(nid_ctx *ctx) {
 
 // A pinned, mapped buffer of n sentinel-filled words for a launch's results, made on first use.  dirty: the previous
 // launch into it was never collected (its wait failed): let it finish, start clean
-int ensure_host_words(nid_ctx *ctx, double *&host, double *&devptr, bool &dirty, size_t n) {
-  if (host && dirty) {
+int ensure_host_words(nid_ctx *ctx, PinnedBuf<double> &words, bool &dirty, size_t n) {
+  if (words && dirty) {
     NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
     NID_HIP(ctx, hipStreamSynchronize(ctx->aux_stream));
-    fill_sentinel(host, n);
+    fill_sentinel(words, n);
     dirty = false;
   }
-  if (host) return NID_OK;
-  if (hipHostMalloc(reinterpret_cast<void **>(&host), n * sizeof(double), hipHostMallocMapped) != hipSuccess) {
-    host = nullptr;
-    return NID_ERR_NOMEM;
-  }
-  fill_sentinel(host, n);
-  NID_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&devptr), host, 0));
+  if (words) return NID_OK;
+  NID_HIP(ctx, words.alloc(n, hipHostMallocMapped));
+  fill_sentinel(words, n);
   return NID_OK;
 }
 int ensure_quad_host(nid_ctx *ctx, Slot &S) {
-  return ensure_host_words(ctx, S.quad_host, S.quad_host_devptr, S.quad_dirty, (size_t)2 * ctx->g.nloc * kDirectRec);
+  return ensure_host_words(ctx, S.quad_host, S.quad_dirty, (size_t)2 * ctx->g.nloc * kDirectRec);
 }
 
 // may this launch be DIRECT?  (timed and diagnostic launches keep the in-launch reduction: they may be re-issued into
@@ -720,8 +711,8 @@ int check_ready(nid_ctx *ctx) {
 
 // timing events of a slot (nid_enable_timing, nid_time_launches): created when first needed
 int timing_events(nid_ctx *ctx, Slot &S) {
-  if (!S.e0) NID_HIP(ctx, hipEventCreate(&S.e0));
-  if (!S.e1) NID_HIP(ctx, hipEventCreate(&S.e1));
+  NID_HIP(ctx, S.e0.ensure());
+  NID_HIP(ctx, S.e1.ensure());
   return NID_OK;
 }
 
@@ -763,16 +754,16 @@ int launch_slot(nid_ctx *ctx, int slot, const Pose &pose, int want_jac, double d
     return NID_OK;
   }
   if (route == Delivery::Groups) {  // the in-launch tail up to the group sums, those straight to the host
-    rc = ensure_host_words(ctx, S.groups_host, S.groups_host_devptr, S.groups_dirty, (size_t)ctx->ngroups * kQuad);
+    rc = ensure_host_words(ctx, S.groups_host, S.groups_dirty, (size_t)ctx->ngroups * kQuad);
     if (rc) return rc;
-    P.slot[0].out_reduced = S.groups_host_devptr;
+    P.slot[0].out_reduced = S.groups_host.dev();
     P.slot[0].host_seq = nullptr;
     P.slot[0].host_quad = 3;
     S.groups_dirty = true;
   } else if (route == Delivery::Direct) {
     rc = ensure_quad_host(ctx, S);
     if (rc) return rc;
-    P.slot[0].quad = S.quad_host_devptr;
+    P.slot[0].quad = S.quad_host.dev();
     P.slot[0].host_quad = 1;
     S.quad_dirty = true;
   }
@@ -923,7 +914,7 @@ int evaluate_common(nid_ctx *ctx, const Pose &pose, int want_jac, double *Ht, do
   EvalParams P{};
   fill_eval_params(ctx, pose, S, std::sqrt(0.95), S.reduced_host_devptr,
                    reinterpret_cast<unsigned long long *>(S.reduced_host_devptr + kReducedLen), &P);
-  P.slot[0].cellout = S.cellout_host_devptr;
+  P.slot[0].cellout = S.cellout_host.dev();
   P.slot[0].cellout_host = 1;
   Delivery route = Delivery::SeqWord;
   if (direct_ok(ctx)) {  // the per-cell outputs straight to the host, word by word, and nothing else (wait_direct_cellout)
@@ -978,17 +969,13 @@ int href_common(nid_ctx *ctx, const Pose &pose, int32_t *bs_counter, double *Hre
     // plus a scalar scatter loop on the host was 1.4 ms of every frame pair (profiles/r04_pair_setup.txt).
     const Geometry &g = ctx->g;
     const size_t N = (size_t)g.rows * g.cols;
-    if (bs_value && (!ctx->bsv_img_dev || !ctx->bsv_stage)) {  // (both or neither: a half-made pair from a failed call is completed)
-      if (!ctx->bsv_img_dev) { int rc = dev_alloc(ctx, &ctx->bsv_img_dev, 4 * N); if (rc) return rc; }
-      if (!ctx->bsv_stage && hipHostMalloc(reinterpret_cast<void **>(&ctx->bsv_stage), 4 * N * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError(); ctx->bsv_stage = nullptr; return NID_ERR_NOMEM;
-      }
+    if (bs_value) {  // (created on first use; a half-made pair from a failed call is completed)
+      NID_HIP(ctx, ctx->bsv_img_dev.grow(4 * N));
+      NID_HIP(ctx, ctx->bsv_stage.grow(4 * N));
     }
-    if (bs_index && (!ctx->bsi_img_dev || !ctx->bsi_stage)) {
-      if (!ctx->bsi_img_dev) { int rc = dev_alloc(ctx, &ctx->bsi_img_dev, N); if (rc) return rc; }
-      if (!ctx->bsi_stage && hipHostMalloc(reinterpret_cast<void **>(&ctx->bsi_stage), N * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError(); ctx->bsi_stage = nullptr; return NID_ERR_NOMEM;
-      }
+    if (bs_index) {
+      NID_HIP(ctx, ctx->bsi_img_dev.grow(N));
+      NID_HIP(ctx, ctx->bsi_stage.grow(N));
     }
     const long total = (long)g.nloc * g.pstride;
     hipLaunchKernelGGL(k_untile_bs, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, g, ctx->t,
@@ -998,7 +985,7 @@ int href_common(nid_ctx *ctx, const Pose &pose, int32_t *bs_counter, double *Hre
     if (whole && bs_value) {
       // bs_value (9.8 MB at 640x480) comes home in kBsParts pieces, each copied out to the caller while the next is
       // still crossing PCIe (the copy-out is as long as the transfer: one after the other they were 0.5 ms)
-      for (int p = 0; p < kBsParts; p++) if (!ctx->bs_part_done[p]) NID_HIP(ctx, hipEventCreateWithFlags(&ctx->bs_part_done[p], hipEventDisableTiming));
+      for (Event &e : ctx->bs_part_done) NID_HIP(ctx, e.ensure(hipEventDisableTiming));
       const size_t part = ((4 * N / kBsParts) + 7) & ~(size_t)7;
       for (int p = 0; p < kBsParts; p++) {
         const size_t lo = std::min(4 * N, part * p), hi = p == kBsParts - 1 ? 4 * N : std::min(4 * N, part * (p + 1));
@@ -1049,7 +1036,7 @@ int upload_tiles(nid_ctx *ctx, const double *depth_m, const double *points3d, co
     NID_HIP(ctx, hipMemcpyAsync(ctx->Twc_dev, Twc, 16 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     depth_dev = ctx->depth_dev;
   } else {
-    if (!ctx->points_dev) { int rc = dev_alloc(ctx, &ctx->points_dev, 3 * N); if (rc) return rc; }
+    NID_HIP(ctx, ctx->points_dev.grow(3 * N));  // (created on first use)
     NID_HIP(ctx, hipMemcpyAsync(ctx->points_dev, points3d, 3 * N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     points_dev = ctx->points_dev;
   }
@@ -1084,10 +1071,8 @@ int pair_stage_ensure(nid_ctx *ctx) {
   const Geometry &g = ctx->g;
   const size_t N = (size_t)g.rows * g.cols;
   const PairStage L = pair_stage_layout(g);
-  if (!ctx->depth16_dev) NID_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->depth16_dev), N * sizeof(uint16_t)));
-  if (!ctx->pair_stage && hipHostMalloc(reinterpret_cast<void **>(&ctx->pair_stage), L.bytes, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError(); ctx->pair_stage = nullptr; return NID_ERR_NOMEM;
-  }
+  NID_HIP(ctx, ctx->depth16_dev.grow(N));
+  NID_HIP(ctx, ctx->pair_stage.grow(L.bytes));
   return NID_OK;
 }
 
@@ -1232,10 +1217,10 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   // 32-bit byte offsets into the reference weights (load_tile_w): 4 x 8 B x nloc x pstride < 2^32
   if ((size_t)g.nloc * (size_t)g.pstride >= ((size_t)1 << 27)) { delete ctx; return NID_ERR_UNSUPPORTED; }
   if (g.nloc >= (1 << 16)) { delete ctx; return NID_ERR_UNSUPPORTED; }  // a repair-queue entry is pose << 16 | cell (k_repair)
-  auto fail = [&](int rc) { nid_destroy(ctx); return rc; };
-  if (hipSetDevice(cfg->device) != hipSuccess) return fail(NID_ERR_NO_DEVICE);
-  if (hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) return fail(NID_ERR_HIP);
-  if (hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess) return fail(NID_ERR_HIP);
+  struct Guard { nid_ctx *c; ~Guard() { if (c) nid_destroy(c); } } guard{ctx};  // (every failure below gives back what was created)
+  if (hipSetDevice(cfg->device) != hipSuccess) return NID_ERR_NO_DEVICE;
+  NID_HIP(ctx, ctx->own_stream.create());
+  NID_HIP(ctx, ctx->aux_stream.create());
   ctx->stream = ctx->own_stream;
   const size_t N = (size_t)g.rows * g.cols;
   const size_t plane = (size_t)g.nloc * g.pstride;
@@ -1243,130 +1228,83 @@ int nid_create_strided(const nid_config *cfg, int32_t cell_stride, nid_ctx **out
   ctx->group_size = direct_group_size(g.nloc);
   ctx->ngroups = (g.nloc + ctx->group_size - 1) / ctx->group_size;
   ctx->sz = pose_sizes(g.nloc, ctx->ngroups);
-  int rc;
-  if ((rc = dev_alloc(ctx, &ctx->t.X, plane))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->t.Y, plane))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->t.Z, plane))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->t.W, 4 * plane))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->t.JR, plane))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->t.I0, plane))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->im1_dev, N + 64))) return fail(rc);
+  nid_ctx::TileBufs &tb = ctx->tiles;
+  NID_HIP(ctx, tb.X.alloc(plane));
+  NID_HIP(ctx, tb.Y.alloc(plane));
+  NID_HIP(ctx, tb.Z.alloc(plane));
+  NID_HIP(ctx, tb.W.alloc(4 * plane));
+  NID_HIP(ctx, tb.JR.alloc(plane));
+  NID_HIP(ctx, tb.I0.alloc(plane));
+  ctx->t = Tiles{tb.X, tb.Y, tb.Z, tb.W, tb.JR, tb.I0};
+  NID_HIP(ctx, ctx->im1_dev.alloc(N + 64));
   {
     // int16 image with margins: (rows + 1) rows of `stride` elements, plus slack for the windows of lanes
     // without a sample (origin (0,0): rows 0..3) on images of fewer than 4 rows
     ctx->im1_stride = (g.cols + 1 + 3) & ~3;
     const size_t n16 = (size_t)(g.rows + 5) * ctx->im1_stride + 64;
-    if ((rc = dev_alloc(ctx, &ctx->im1s_dev, n16))) return fail(rc);
-    if (hipMemset(ctx->im1s_dev, 0, n16 * sizeof(int16_t)) != hipSuccess) return fail(NID_ERR_HIP);
+    NID_HIP(ctx, ctx->im1s_dev.alloc(n16));
+    NID_HIP(ctx, hipMemset(ctx->im1s_dev, 0, n16 * sizeof(int16_t)));
   }
-  if ((rc = dev_alloc(ctx, &ctx->im0_dev, N))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->depth_dev, N))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->Twc_dev, 16))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->Nc_dev, g.nloc))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->Href_dev, g.nloc))) return fail(rc);
-  if ((rc = dev_alloc(ctx, &ctx->repair_count_dev, 1))) return fail(rc);
-  if (hipMemset(ctx->repair_count_dev, 0, sizeof(unsigned long long)) != hipSuccess) return fail(NID_ERR_HIP);
-  for (int q = 0; q < 2; q++) {  // one queue per launch stream: [count | exit ticket | (pose << 16 | cell, repair set x 2) ...], see k_repair
+  NID_HIP(ctx, ctx->im0_dev.alloc(N));
+  NID_HIP(ctx, ctx->depth_dev.alloc(N));
+  NID_HIP(ctx, ctx->Twc_dev.alloc(16));
+  NID_HIP(ctx, ctx->Nc_dev.alloc(g.nloc));
+  NID_HIP(ctx, ctx->Href_dev.alloc(g.nloc));
+  NID_HIP(ctx, ctx->repair_count_dev.alloc(1));
+  NID_HIP(ctx, hipMemset(ctx->repair_count_dev, 0, sizeof(unsigned long long)));
+  for (DevBuf<unsigned> &queue : ctx->repair_queue_dev) {  // one queue per launch stream: [count | exit ticket | (pose << 16 | cell, repair set x 2) ...], see k_repair
     const size_t n = 2 + 3 * (size_t)g.nloc * kSeqGridMax;  // (one entry per workgroup of the largest grid at most)
-    if ((rc = dev_alloc(ctx, &ctx->repair_queue_dev[q], n))) return fail(rc);
-    if (hipMemset(ctx->repair_queue_dev[q], 0, n * sizeof(unsigned)) != hipSuccess) return fail(NID_ERR_HIP);
+    NID_HIP(ctx, queue.alloc(n));
+    NID_HIP(ctx, hipMemset(queue, 0, n * sizeof(unsigned)));
   }
   {
     // the evaluation kernels read the table with kWcPre on its value coefficients (k_eval2's hist_add, fx_bits)
     std::vector<double> coef;
     build_coef_table(g.S, &coef);
     for (size_t i = 0; i < coef.size(); i++) if ((i % 7) < 4) coef[i] *= kWcPre;
-    if ((rc = dev_alloc(ctx, &ctx->ctab_dev, coef.size()))) return fail(rc);
-    if (hipMemcpy(ctx->ctab_dev, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      return fail(NID_ERR_HIP);
+    NID_HIP(ctx, ctx->ctab_dev.alloc(coef.size()));
+    NID_HIP(ctx, hipMemcpy(ctx->ctab_dev, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   {
     // Per-slot buffers come out of ONE allocation per kind (NID_SLOTS x 5 hipMalloc + 2 hipHostMalloc calls used to be
     // most of the context's creation time); the slots hold pointers into the slabs.
     const size_t n_cellout = (size_t)g.nloc * kCellOut;
     const size_t n_rhost = kReducedLen + 2;  // [32 doubles][u64 sequence word][pad]
-    if ((rc = dev_alloc(ctx, &ctx->slab_cellout, n_cellout * NID_SLOTS))) return fail(rc);
-    if ((rc = dev_alloc(ctx, &ctx->slab_reduced, (size_t)kReducedLen * NID_SLOTS))) return fail(rc);
-    if ((rc = pool_ensure(ctx, ctx->slot_pool, NID_SLOTS, false))) return fail(rc);  // pose s of it is slot s's (fill_slot_args)
-    if (hipHostMalloc(reinterpret_cast<void **>(&ctx->slab_reduced_host), n_rhost * NID_SLOTS * sizeof(double),
-                      hipHostMallocMapped) != hipSuccess) return fail(NID_ERR_NOMEM);
+    NID_HIP(ctx, ctx->slab_cellout.alloc(n_cellout * NID_SLOTS));
+    NID_HIP(ctx, ctx->slab_reduced.alloc((size_t)kReducedLen * NID_SLOTS));
+    { int rc = pool_ensure(ctx, ctx->slot_pool, NID_SLOTS, false); if (rc) return rc; }  // pose s of it is slot s's (fill_slot_args)
+    NID_HIP(ctx, ctx->slab_reduced_host.alloc(n_rhost * NID_SLOTS, hipHostMallocMapped));
     std::memset(ctx->slab_reduced_host, 0, n_rhost * NID_SLOTS * sizeof(double));
-    double *rhost_dev = nullptr;
-    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&rhost_dev), ctx->slab_reduced_host, 0) != hipSuccess) return fail(NID_ERR_HIP);
     for (int s = 0; s < NID_SLOTS; s++) {
       Slot &S = ctx->slots[s];
       S.cellout_dev = ctx->slab_cellout + n_cellout * s;
       S.reduced_dev = ctx->slab_reduced + (size_t)kReducedLen * s;
-      S.reduced_host = ctx->slab_reduced_host + n_rhost * s;
-      S.reduced_host_devptr = rhost_dev + n_rhost * s;
-      if (hipEventCreateWithFlags(&S.done, hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
+      S.reduced_host = ctx->slab_reduced_host.host() + n_rhost * s;
+      S.reduced_host_devptr = ctx->slab_reduced_host.dev() + n_rhost * s;
+      NID_HIP(ctx, S.done.create(hipEventDisableTiming));
     }
     // the blocking per-cell calls use slot 0 only: its per-cell outputs can go straight to mapped pinned memory
-    Slot &S0 = ctx->slots[0];
-    if (hipHostMalloc(reinterpret_cast<void **>(&S0.cellout_host), n_cellout * sizeof(double), hipHostMallocMapped) != hipSuccess)
-      return fail(NID_ERR_NOMEM);
-    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&S0.cellout_host_devptr), S0.cellout_host, 0) != hipSuccess)
-      return fail(NID_ERR_HIP);
+    NID_HIP(ctx, ctx->slots[0].cellout_host.alloc(n_cellout, hipHostMallocMapped));
   }
   for (int r = 0; r < nid_ctx::kExtRing; r++) {
-    if ((rc = dev_alloc(ctx, &ctx->ext_dev[r], (size_t)kMaxBatchExt))) return fail(rc);
-    if (hipHostMalloc(reinterpret_cast<void **>(&ctx->ext_host[r]), (size_t)kMaxBatchExt * sizeof(SlotArgs),
-                      hipHostMallocDefault) != hipSuccess) return fail(NID_ERR_NOMEM);
-    if (hipEventCreateWithFlags(&ctx->ext_done[r], hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
+    NID_HIP(ctx, ctx->ext_dev[r].alloc((size_t)kMaxBatchExt));
+    NID_HIP(ctx, ctx->ext_host[r].alloc((size_t)kMaxBatchExt));
+    NID_HIP(ctx, ctx->ext_done[r].create(hipEventDisableTiming));
   }
+  guard.c = nullptr;
   *out = ctx;
   return NID_OK;
 }
 
+// Ordering only: what the context owns releases itself at `delete ctx` (nid_hip_owned.h), buffers and events before the
+// streams (nid_ctx's member order) -- with no resident kernel on the device and the streams drained.
 int nid_destroy(nid_ctx *ctx) {
   if (!ctx) return NID_OK;
   (void)hipSetDevice(ctx->cfg.device);
   resident_retire(ctx);
-  if (ctx->res.stream) (void)hipStreamDestroy(ctx->res.stream);
-  if (ctx->res.ctl) (void)hipFree(ctx->res.ctl);
-  if (ctx->res.rec_host) (void)hipHostFree(ctx->res.rec_host);
-  if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-  (void)hipFree(ctx->t.X); (void)hipFree(ctx->t.Y); (void)hipFree(ctx->t.Z); (void)hipFree(ctx->t.W);
-  (void)hipFree(ctx->t.JR); (void)hipFree(ctx->t.I0);
-  (void)hipFree(ctx->im1_dev); (void)hipFree(ctx->im1s_dev); (void)hipFree(ctx->im0_dev); (void)hipFree(ctx->depth_dev);
-  (void)hipFree(ctx->points_dev); (void)hipFree(ctx->Twc_dev); (void)hipFree(ctx->depth16_dev);
-  if (ctx->pair_stage) (void)hipHostFree(ctx->pair_stage);
-  (void)hipFree(ctx->Nc_dev); (void)hipFree(ctx->Href_dev); (void)hipFree(ctx->ctab_dev); (void)hipFree(ctx->repair_count_dev);
-  (void)hipFree(ctx->bsv_img_dev); (void)hipFree(ctx->bsi_img_dev);
-  if (ctx->bsv_stage) (void)hipHostFree(ctx->bsv_stage);
-  if (ctx->bsi_stage) (void)hipHostFree(ctx->bsi_stage);
-  for (hipEvent_t e : ctx->bs_part_done) if (e) (void)hipEventDestroy(e);
-  (void)hipFree(ctx->repair_queue_dev[0]); (void)hipFree(ctx->repair_queue_dev[1]);
-  (void)hipFree(ctx->dbg_u); (void)hipFree(ctx->dbg_v); (void)hipFree(ctx->dbg_ic);
-  (void)hipFree(ctx->dbg_wc); (void)hipFree(ctx->dbg_jc); (void)hipFree(ctx->dbg_stamps);
-  for (int r = 0; r < nid_ctx::kSeqRing; r++) {
-    (void)hipFree(ctx->seq_dev[r]);
-    if (ctx->seq_host[r]) (void)hipHostFree(ctx->seq_host[r]);
-    if (ctx->seq_done[r]) (void)hipEventDestroy(ctx->seq_done[r]);
-    if (ctx->seq_fence[r]) (void)hipEventDestroy(ctx->seq_fence[r]);
-  }
-  if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-  pool_free(ctx->pool.poses);
-  free_ms_pool(ctx);
-  pool_free(ctx->slot_pool);
-  (void)hipFree(ctx->slab_cellout); (void)hipFree(ctx->slab_reduced);
-  if (ctx->slab_reduced_host) (void)hipHostFree(ctx->slab_reduced_host);
-  for (int s = 0; s < NID_SLOTS; s++) {
-    Slot &S = ctx->slots[s];
-    if (S.cellout_host) (void)hipHostFree(S.cellout_host);
-    if (S.quad_host) (void)hipHostFree(S.quad_host);
-    if (S.groups_host) (void)hipHostFree(S.groups_host);
-    if (S.done) (void)hipEventDestroy(S.done);
-    if (S.e0) (void)hipEventDestroy(S.e0);
-    if (S.e1) (void)hipEventDestroy(S.e1);
-  }
-  for (int r = 0; r < nid_ctx::kExtRing; r++) {
-    (void)hipFree(ctx->ext_dev[r]);
-    if (ctx->ext_host[r]) (void)hipHostFree(ctx->ext_host[r]);
-    if (ctx->ext_done[r]) (void)hipEventDestroy(ctx->ext_done[r]);
-  }
-  if (ctx->aux_stream) { (void)hipStreamSynchronize(ctx->aux_stream); (void)hipStreamDestroy(ctx->aux_stream); }
-  if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
+  for (hipStream_t st : {ctx->own_stream.get(), ctx->copy_stream.get(), ctx->aux_stream.get()})
+    if (st) (void)hipStreamSynchronize(st);
+  if (ctx->res.ctl) (void)hipFree(ctx->res.ctl);  // (the mailbox: hipExtMallocWithFlags, no owner type)
   delete ctx;
   return NID_OK;
 }
@@ -1466,7 +1404,7 @@ int nid_get_points3d(nid_ctx *ctx, double *points3d) {
   if (!ctx->have_ref) return NID_ERR_STATE;
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   const size_t N = (size_t)ctx->g.rows * ctx->g.cols;
-  if (!ctx->points_dev) { int rc = dev_alloc(ctx, &ctx->points_dev, 3 * N); if (rc) return rc; }
+  NID_HIP(ctx, ctx->points_dev.grow(3 * N));  // (created on first use)
   if (ctx->ref_from_depth) {
     hipLaunchKernelGGL(k_backproject_plain, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream,
                        ctx->g, ctx->depth_dev, ctx->Twc_dev, ctx->points_dev);
@@ -1485,31 +1423,31 @@ namespace {
 // nid_backproject_release() -- called by nid_legacy_reset -- gives the ~25 MB per 640x480 back.
 constexpr int kBpParts = 4;
 struct BackprojectScratch {
-  int device = -1;
-  size_t cap = 0;
-  double *d_depth = nullptr, *d_T = nullptr, *d_pts = nullptr, *h_stage = nullptr;  // h_stage: [max(3 cap, cap + 16)] pinned
-  hipStream_t stream = nullptr;
-  hipEvent_t part_done[kBpParts] = {};
-  bool make_events() {
-    for (hipEvent_t &e : part_done)
-      if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
-    return true;
+  int device;
+  Stream stream;
+  DevBuf<double> d_depth, d_T, d_pts;  // [N], [16], [3 N]
+  PinnedBuf<double> h_stage;           // [max(3 N, N + 16)]: depth + the 4x4 pose go down through it (more than 3 N for images of fewer than 8 pixels)
+  Event part_done[kBpParts];
+  bool make(size_t N) {
+    bool ok = d_depth.alloc(N) == hipSuccess && d_T.alloc(16) == hipSuccess && d_pts.alloc(3 * N) == hipSuccess &&
+              h_stage.alloc(std::max(3 * N, N + 16)) == hipSuccess && stream.create() == hipSuccess;
+    for (Event &e : part_done) ok = ok && e.create(hipEventDisableTiming) == hipSuccess;
+    return ok;
   }
-  void release() {
-    if (device >= 0) (void)hipSetDevice(device);
-    (void)hipFree(d_depth); (void)hipFree(d_T); (void)hipFree(d_pts);
-    if (h_stage) (void)hipHostFree(h_stage);
-    if (stream) (void)hipStreamDestroy(stream);
-    for (hipEvent_t e : part_done) if (e) (void)hipEventDestroy(e);
-    *this = BackprojectScratch();
-  }
-} g_bp;
+};
+BackprojectScratch *g_bp = nullptr;  // (on the heap: nothing of it is released behind the runtime at process exit)
 std::mutex g_bp_mutex;
+void backproject_release() {
+  if (!g_bp) return;
+  (void)hipSetDevice(g_bp->device);
+  delete g_bp;
+  g_bp = nullptr;
+}
 }  // namespace
 
 int nid_backproject_release(void) {
   std::lock_guard<std::mutex> lock(g_bp_mutex);
-  g_bp.release();
+  backproject_release();
   return NID_OK;
 }
 
@@ -1522,22 +1460,13 @@ int nid_backproject(const double *depth_m, const double *T_wc0, double fx, doubl
   if (device < 0 || device >= ndev || hipSetDevice(device) != hipSuccess) return NID_ERR_INVALID_ARG;
   const size_t N = (size_t)rows * cols;
   std::lock_guard<std::mutex> lock(g_bp_mutex);
-  BackprojectScratch &B = g_bp;
-  if (B.device != device || B.cap < N) {
-    B.release();
+  if (!g_bp || g_bp->device != device || g_bp->d_depth.size() < N) {
+    backproject_release();
     if (hipSetDevice(device) != hipSuccess) return NID_ERR_INVALID_ARG;
-    if (hipMalloc(reinterpret_cast<void **>(&B.d_depth), N * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&B.d_T), 16 * 8) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&B.d_pts), 3 * N * 8) != hipSuccess ||
-        // (depth + the 4x4 pose go down through it: N + 16 doubles, more than 3 N for images of fewer than 8 pixels)
-        hipHostMalloc(reinterpret_cast<void **>(&B.h_stage), std::max(3 * N, N + 16) * 8, hipHostMallocDefault) != hipSuccess ||
-        hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking) != hipSuccess || !B.make_events()) {
-      (void)hipGetLastError();
-      B.release();
-      return NID_ERR_NOMEM;
-    }
-    B.device = device; B.cap = N;
+    g_bp = new (std::nothrow) BackprojectScratch{device};
+    if (!g_bp || !g_bp->make(N)) { backproject_release(); return NID_ERR_NOMEM; }
   }
+  BackprojectScratch &B = *g_bp;
   Geometry g{};
   g.rows = rows; g.cols = cols; g.fx = fx; g.fy = fy; g.cx = cx; g.cy = cy;
   // depth and pose go down through the pinned block (its first N + 16 doubles), the points come back into all of it
@@ -1638,18 +1567,18 @@ int nid_plain_nid(nid_ctx *ctx, const double *pose7, int bins, double *Href, dou
   if (!ctx || !pose7 || bins < 1 || bins > kMaxPlainBins) return NID_ERR_INVALID_ARG;
   if (!ctx->have_ref || !ctx->have_target) { ctx->last_error = "reference / target not set"; return NID_ERR_STATE; }
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
-  resident_retire(ctx);  // (hipFree below waits for the whole device)
+  resident_retire(ctx);  // (the release below waits for the whole device)
   Pose p; pose_from_pose7(pose7, NID_XFORM_MATRIX, &p);  // T_cw1 * pw as a 4x4 product (:353-354)
   const int nloc = ctx->g.nloc;
-  double *out_dev = nullptr;
-  NID_HIP(ctx, hipMalloc(&out_dev, (size_t)nloc * 6 * sizeof(double)));
+  DevBuf<double> out_dev;
+  NID_HIP(ctx, out_dev.alloc((size_t)nloc * 6));
   hipLaunchKernelGGL((k_plain_nid<256>), dim3(nloc), dim3(256), 0, ctx->stream, ctx->g, p, ctx->t, ctx->im1_dev, bins,
                      out_dev);
   std::vector<double> o((size_t)nloc * 6);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(o.data(), out_dev, o.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(out_dev);
+  out_dev.reset();
   NID_HIP(ctx, e);
   double sum = 0.0;
   for (int cl = 0; cl < nloc; cl++) {
@@ -1775,21 +1704,17 @@ int nid_launch_batch_to(nid_ctx *ctx, int first_slot, int n, const double *poses
 namespace {
 // result buffers (device + pinned host), events and the copy stream of the pipelined loop, for launches of `batch` poses
 int ensure_seq_ring(nid_ctx *ctx, int batch) {
-  if (ctx->seq_cap >= (size_t)batch) return NID_OK;
-  resident_retire(ctx);  // (hipFree waits for the whole device)
+  const size_t n = (size_t)batch * kReducedLen;
+  // (copy_stream is made last: where it exists, so does every event)
+  if (ring_size(ctx->seq_dev) >= n && ring_size(ctx->seq_host) >= n && ctx->copy_stream) return NID_OK;
+  resident_retire(ctx);  // (a release waits for the whole device)
   for (int r = 0; r < nid_ctx::kSeqRing; r++) {
-    (void)hipFree(ctx->seq_dev[r]); ctx->seq_dev[r] = nullptr;
-    if (ctx->seq_host[r]) (void)hipHostFree(ctx->seq_host[r]);
-    ctx->seq_host[r] = nullptr;
-    int rc = dev_alloc(ctx, &ctx->seq_dev[r], (size_t)batch * kReducedLen);
-    if (rc) return rc;
-    if (hipHostMalloc(reinterpret_cast<void **>(&ctx->seq_host[r]), (size_t)batch * kReducedLen * sizeof(double),
-                      hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
-    if (!ctx->seq_done[r]) NID_HIP(ctx, hipEventCreateWithFlags(&ctx->seq_done[r], hipEventDisableTiming));
-    if (!ctx->seq_fence[r]) NID_HIP(ctx, hipEventCreateWithFlags(&ctx->seq_fence[r], hipEventDisableTiming));
+    NID_HIP(ctx, ctx->seq_dev[r].grow(n));
+    NID_HIP(ctx, ctx->seq_host[r].grow(n));
+    NID_HIP(ctx, ctx->seq_done[r].ensure(hipEventDisableTiming));
+    NID_HIP(ctx, ctx->seq_fence[r].ensure(hipEventDisableTiming));
   }
-  if (!ctx->copy_stream) NID_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-  ctx->seq_cap = (size_t)batch;
+  NID_HIP(ctx, ctx->copy_stream.ensure());
   return NID_OK;
 }
 
@@ -1993,12 +1918,11 @@ int nid_debug_enable_pixel_dump(nid_ctx *ctx, int enable) {
   resident_retire(ctx);
   if (enable && !ctx->dbg_u) {
     const size_t N = (size_t)ctx->g.rows * ctx->g.cols;
-    int rc;
-    if ((rc = dev_alloc(ctx, &ctx->dbg_u, N))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->dbg_v, N))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->dbg_ic, N))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->dbg_wc, 4 * N))) return rc;
-    if ((rc = dev_alloc(ctx, &ctx->dbg_jc, N))) return rc;
+    NID_HIP(ctx, ctx->dbg_jc.alloc(N));
+    NID_HIP(ctx, ctx->dbg_v.alloc(N));
+    NID_HIP(ctx, ctx->dbg_ic.alloc(N));
+    NID_HIP(ctx, ctx->dbg_wc.alloc(4 * N));
+    NID_HIP(ctx, ctx->dbg_u.alloc(N));  // (the last: the dump exists when dbg_u does)
   }
   ctx->dbg_enabled = enable != 0;
   ctx->dbg_jac = enable == 2 ? 1 : 0;
@@ -2035,13 +1959,11 @@ int nid_debug_enable_stamps(nid_ctx *ctx, int enable) {
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   resident_retire(ctx);
   if (enable && !ctx->dbg_stamps) {
-    int rc = dev_alloc(ctx, &ctx->dbg_stamps, (size_t)ctx->g.nloc * 10);
-    if (rc) return rc;
+    NID_HIP(ctx, ctx->dbg_stamps.alloc((size_t)ctx->g.nloc * 10));
     NID_HIP(ctx, hipMemset(ctx->dbg_stamps, 0, (size_t)ctx->g.nloc * 10 * sizeof(long long)));
   } else if (!enable && ctx->dbg_stamps) {
     NID_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->dbg_stamps);
-    ctx->dbg_stamps = nullptr;
+    ctx->dbg_stamps.reset();
   }
   return NID_OK;
 }

@@ -57,10 +57,10 @@ int resident_probe(nid_ctx *ctx) {
   }
   auto fail = [&](const char *what, int rc) {  // every failure path gives back what was created
     (void)hipGetLastError();
-    (void)hipFree(p);
-    if (R.stream) { (void)hipStreamDestroy(R.stream); R.stream = nullptr; }
-    if (R.rec_host) { (void)hipHostFree(R.rec_host); R.rec_host = nullptr; }
-    R.ctl = nullptr; R.rec_devptr = nullptr;
+    (void)hipFree(p);  // (the mailbox: the one raw allocation of the unit)
+    R.ctl = nullptr;
+    R.stream.reset();
+    R.rec_host.reset();
     R.why = what;
     return rc;
   };
@@ -68,11 +68,10 @@ int resident_probe(nid_ctx *ctx) {
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   if (e != hipSuccess) return fail("clearing the mailbox failed", NID_ERR_UNSUPPORTED);
   R.ctl = static_cast<ResidentCtl *>(p);
-  if (hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking) != hipSuccess) return fail("no stream for the resident kernel", NID_ERR_HIP);
+  if (R.stream.create() != hipSuccess) return fail("no stream for the resident kernel", NID_ERR_HIP);
   const size_t n = (size_t)2 * ctx->g.nloc * kDirectRec;
-  if (hipHostMalloc(reinterpret_cast<void **>(&R.rec_host), n * sizeof(double), hipHostMallocMapped) != hipSuccess) return fail("no pinned memory for the records", NID_ERR_NOMEM);
+  if (R.rec_host.alloc(n, hipHostMallocMapped) != hipSuccess) return fail("no pinned memory for the records", NID_ERR_NOMEM);
   fill_sentinel(R.rec_host, n);
-  if (hipHostGetDevicePointer(reinterpret_cast<void **>(&R.rec_devptr), R.rec_host, 0) != hipSuccess) return fail("hipHostGetDevicePointer failed", NID_ERR_HIP);
   R.probed = 1;
   return NID_OK;
 }
@@ -132,8 +131,8 @@ int resident_start(nid_ctx *ctx, int nt) {
   set_hist_params(P);
   SlotArgs &A = P.slot[0];
   Slot &S0 = ctx->slots[0];
-  A.cellout = S0.cellout_host_devptr;
-  A.quad = R.rec_devptr;
+  A.cellout = S0.cellout_host.dev();
+  A.quad = R.rec_host.dev();
   A.gpart = nullptr; A.ticket = nullptr; A.out_reduced = nullptr; A.host_seq = nullptr;
   A.launch_seq = 0; A.cellout_host = 0; A.host_quad = 1;
   // eval_cell's LDS + the cell's tile entries (k_eval2's LAT branch, RES): rounds x threads x (7 doubles + 1 int)
@@ -256,10 +255,10 @@ int resident_fallback(nid_ctx *ctx, Slot &S) {
   fill_common_params(ctx, 1.0, &P);
   SlotArgs &A = P.slot[0];
   fill_slot_args(ctx, R.pose, S, nullptr, nullptr, &A);
-  A.quad = S.quad_host_devptr;
+  A.quad = S.quad_host.dev();
   A.host_quad = R.want_cellout ? 2 : 1;
   S.quad_dirty = !R.want_cellout;
-  if (R.want_cellout) { A.cellout = ctx->slots[0].cellout_host_devptr; A.cellout_host = 1; }
+  if (R.want_cellout) { A.cellout = ctx->slots[0].cellout_host.dev(); A.cellout_host = 1; }
   NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
   S.delivery = R.want_cellout ? Delivery::Cellout : Delivery::Direct;  // from here on the wait is an ordinary one
   R.pending_slot = -1;

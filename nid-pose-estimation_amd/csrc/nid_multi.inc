@@ -74,15 +74,14 @@ RcclApi g_rccl;
 
 constexpr int kGroupRing = 2;  // nid_multi_run_sequence: groups in flight
 
-struct ShardBuf {
-  double *part_dev = nullptr;    // [NID_SLOTS][32] partial blocks of launches in RCCL mode
-  double *cells_dev = nullptr;   // [ncell][kCellExch] per-cell exchange across processes
-  hipStream_t comm_stream = nullptr;
-  hipEvent_t fence[2] = {nullptr, nullptr};  // compute streams -> comm stream
-  double *ring_dev[kGroupRing] = {nullptr, nullptr};  // run_sequence: [group*batch][32]
-  hipEvent_t ring_free[kGroupRing] = {nullptr, nullptr};  // this shard's exchange of the group in ring_dev[i] is over
+struct ShardBuf {  // (released on the shard's device, before its context: nid_multi_destroy)
+  Stream comm_stream;
+  DevBuf<double> part_dev;    // [NID_SLOTS][32] partial blocks of launches in RCCL mode
+  DevBuf<double> cells_dev;   // [ncell][kCellExch] per-cell exchange across processes
+  Event fence[2];             // compute streams -> comm stream
+  DevBuf<double> ring_dev[kGroupRing];  // run_sequence: each at least [group*batch][32]
+  Event ring_free[kGroupRing];          // this shard's exchange of the group in ring_dev[i] is over
   bool ring_used[kGroupRing] = {false, false};
-  size_t ring_cap = 0;
 };
 constexpr int kCellExch = 9;  // Htarget, Hjoint, err, der[6]
 
@@ -111,12 +110,11 @@ struct nid_multi {
   int reduce_mode = NID_REDUCE_HOST;
   bool comm_live = false;
   // RCCL mode: results of batched launches land here (pinned), one event per batch
-  double *part_host = nullptr;   // [NID_SLOTS][32]
-  double *cells_host = nullptr;  // [ncell][kCellExch]
-  double *ring_host[kGroupRing] = {nullptr, nullptr};
-  size_t ring_host_cap = 0;  // blocks each of them holds
-  hipEvent_t ring_done[kGroupRing] = {nullptr, nullptr};
-  hipEvent_t batch_done[NID_SLOTS];
+  PinnedBuf<double> part_host;   // [NID_SLOTS][32]
+  PinnedBuf<double> cells_host;  // [ncell][kCellExch]
+  PinnedBuf<double> ring_host[kGroupRing];  // each at least [shards * group*batch][32]
+  Event ring_done[kGroupRing];
+  Event batch_done[NID_SLOTS];
   int batch_of[NID_SLOTS];       // first slot of the batch a pending slot belongs to, -1 = not pending
   std::string last_error;
 };
@@ -128,7 +126,7 @@ namespace {
     hipError_t _e = (expr);                                                    \
     if (_e != hipSuccess) {                                                    \
       (m)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);     \
-      return NID_ERR_HIP;                                                      \
+      return _e == hipErrorOutOfMemory ? NID_ERR_NOMEM : NID_ERR_HIP;          \
     }                                                                          \
   } while (0)
 #define NIDM_NCCL(m, expr)                                                     \
@@ -162,21 +160,21 @@ int multi_check(nid_multi *m) {
 int multi_alloc(nid_multi *m) {
   const size_t K = m->sh.size();
   m->buf.resize(K);
-  for (int s = 0; s < NID_SLOTS; s++) { m->batch_done[s] = nullptr; m->batch_of[s] = -1; m->batch_n[s] = 0; }
+  for (int s = 0; s < NID_SLOTS; s++) { m->batch_of[s] = -1; m->batch_n[s] = 0; }
   for (size_t k = 0; k < K; k++) {
     NIDM_HIP(m, hipSetDevice(m->sh[k]->cfg.device));
     ShardBuf &B = m->buf[k];
-    NIDM_HIP(m, hipMalloc(reinterpret_cast<void **>(&B.part_dev), (size_t)NID_SLOTS * kReducedLen * sizeof(double)));
-    NIDM_HIP(m, hipMalloc(reinterpret_cast<void **>(&B.cells_dev), (size_t)m->ncell * kCellExch * sizeof(double)));
-    NIDM_HIP(m, hipStreamCreateWithFlags(&B.comm_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) NIDM_HIP(m, hipEventCreateWithFlags(&B.fence[i], hipEventDisableTiming));
-    for (int i = 0; i < kGroupRing; i++) NIDM_HIP(m, hipEventCreateWithFlags(&B.ring_free[i], hipEventDisableTiming));
+    NIDM_HIP(m, B.part_dev.alloc((size_t)NID_SLOTS * kReducedLen));
+    NIDM_HIP(m, B.cells_dev.alloc((size_t)m->ncell * kCellExch));
+    NIDM_HIP(m, B.comm_stream.create());
+    for (Event &e : B.fence) NIDM_HIP(m, e.create(hipEventDisableTiming));
+    for (Event &e : B.ring_free) NIDM_HIP(m, e.create(hipEventDisableTiming));
   }
   NIDM_HIP(m, hipSetDevice(m->sh[0]->cfg.device));
-  NIDM_HIP(m, hipHostMalloc(reinterpret_cast<void **>(&m->part_host), (size_t)NID_SLOTS * kReducedLen * sizeof(double), hipHostMallocDefault));
-  NIDM_HIP(m, hipHostMalloc(reinterpret_cast<void **>(&m->cells_host), (size_t)m->ncell * kCellExch * sizeof(double), hipHostMallocDefault));
-  for (int s = 0; s < NID_SLOTS; s++) NIDM_HIP(m, hipEventCreateWithFlags(&m->batch_done[s], hipEventDisableTiming));
-  for (int i = 0; i < kGroupRing; i++) NIDM_HIP(m, hipEventCreateWithFlags(&m->ring_done[i], hipEventDisableTiming));
+  NIDM_HIP(m, m->part_host.alloc((size_t)NID_SLOTS * kReducedLen));
+  NIDM_HIP(m, m->cells_host.alloc((size_t)m->ncell * kCellExch));
+  for (Event &e : m->batch_done) NIDM_HIP(m, e.create(hipEventDisableTiming));
+  for (Event &e : m->ring_done) NIDM_HIP(m, e.create(hipEventDisableTiming));
   return NID_OK;
 }
 
@@ -360,31 +358,18 @@ int nid_multi_create_partitioned(const nid_config *cfg, const int32_t *devices, 
 
 int nid_multi_destroy(nid_multi *m) {
   if (!m) return NID_OK;
-  // resident evaluators first: every hipFree below synchronises the device, i.e. would wait for a resident kernel to
+  // resident evaluators first: every release below synchronises the device, i.e. would wait for a resident kernel to
   // leave by itself (its 200 ms idle limit) instead of being told to
   for (nid_ctx *ctx : m->sh) (void)nid_set_resident(ctx, 0);
-  for (size_t k = 0; k < m->sh.size(); k++) {
+  for (size_t k = 0; k < m->sh.size() && k < m->buf.size(); k++) {  // a shard's buffers on its device, behind its comm stream
     (void)hipSetDevice(m->sh[k]->cfg.device);
-    if (k < m->buf.size()) {
-      ShardBuf &B = m->buf[k];
-      if (B.comm_stream) (void)hipStreamSynchronize(B.comm_stream);
-      (void)hipFree(B.part_dev); (void)hipFree(B.cells_dev);
-      for (int i = 0; i < kGroupRing; i++) (void)hipFree(B.ring_dev[i]);
-      for (int i = 0; i < 2; i++) if (B.fence[i]) (void)hipEventDestroy(B.fence[i]);
-      for (int i = 0; i < kGroupRing; i++) if (B.ring_free[i]) (void)hipEventDestroy(B.ring_free[i]);
-      if (B.comm_stream) (void)hipStreamDestroy(B.comm_stream);
-    }
+    if (m->buf[k].comm_stream) (void)hipStreamSynchronize(m->buf[k].comm_stream);
+    m->buf[k] = ShardBuf();
   }
-  if (!m->sh.empty()) (void)hipSetDevice(m->sh[0]->cfg.device);
-  if (m->part_host) (void)hipHostFree(m->part_host);
-  if (m->cells_host) (void)hipHostFree(m->cells_host);
-  for (int i = 0; i < kGroupRing; i++) {
-    if (m->ring_host[i]) (void)hipHostFree(m->ring_host[i]);
-    if (m->ring_done[i]) (void)hipEventDestroy(m->ring_done[i]);
-  }
-  for (int s = 0; s < NID_SLOTS; s++) if (m->batch_done[s]) (void)hipEventDestroy(m->batch_done[s]);
+  const int dev0 = m->sh.empty() ? -1 : m->sh[0]->cfg.device;
   if (m->owns_comm && m->attached) nid_comm_destroy(m->attached);
   for (nid_ctx *ctx : m->sh) nid_destroy(ctx);
+  if (dev0 >= 0) (void)hipSetDevice(dev0);  // (the pinned landing zones and the events are the first shard's device's)
   delete m;
   return NID_OK;
 }
@@ -745,18 +730,20 @@ int nid_multi_time_exchange(nid_multi *m, int blocks, int repeats, float *ms_per
   const size_t K = m->sh.size(), count = (size_t)blocks * kReducedLen;
   std::vector<double *> dev(K, nullptr);
   std::vector<hipStream_t> st(K, nullptr);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  // every exit path releases what was created (a HIP error used to leave the buffers and events behind)
+  std::vector<DevBuf<double>> own(K);
+  Event e0, e1;
+  // every exit path releases what was created: each buffer on its device, behind its stream
   auto body = [&]() -> int {
     for (size_t k = 0; k < K; k++) {
       NIDM_HIP(m, hipSetDevice(m->sh[k]->cfg.device));
-      NIDM_HIP(m, hipMalloc(reinterpret_cast<void **>(&dev[k]), count * sizeof(double)));
+      NIDM_HIP(m, own[k].alloc(count));
+      dev[k] = own[k];
       st[k] = m->buf[k].comm_stream;
       NIDM_HIP(m, hipMemsetAsync(dev[k], 0, count * sizeof(double), st[k]));
     }
     NIDM_HIP(m, hipSetDevice(m->sh[0]->cfg.device));
-    NIDM_HIP(m, hipEventCreate(&e0));
-    NIDM_HIP(m, hipEventCreate(&e1));
+    NIDM_HIP(m, e0.create());
+    NIDM_HIP(m, e1.create());
     int r2 = multi_allreduce(m, dev, count, st);  // warm
     if (r2 != NID_OK) return r2;
     NIDM_HIP(m, hipSetDevice(m->sh[0]->cfg.device));
@@ -777,10 +764,8 @@ int nid_multi_time_exchange(nid_multi *m, int blocks, int repeats, float *ms_per
   for (size_t k = 0; k < K; k++) {
     (void)hipSetDevice(m->sh[k]->cfg.device);
     if (st[k]) (void)hipStreamSynchronize(st[k]);
-    if (dev[k]) (void)hipFree(dev[k]);
+    own[k].reset();
   }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
   return rc;
 }
 
@@ -822,25 +807,13 @@ static int multi_run_sequence_impl(nid_multi *m, const double *poses7, int n, in
   const size_t host_blocks = rccl ? gcap : gcap * K;  // host mode: every shard's partial blocks come home
   for (size_t k = 0; k < K; k++) {
     ShardBuf &B = m->buf[k];
-    if (B.ring_cap < gcap) {
+    if (ring_size(B.ring_dev) < gcap * kReducedLen) {
       NIDM_HIP(m, hipSetDevice(m->sh[k]->cfg.device));
-      for (int i = 0; i < kGroupRing; i++) {
-        (void)hipFree(B.ring_dev[i]);
-        B.ring_dev[i] = nullptr;
-        NIDM_HIP(m, hipMalloc(reinterpret_cast<void **>(&B.ring_dev[i]), gcap * kReducedLen * sizeof(double)));
-      }
-      B.ring_cap = gcap;
+      NIDM_HIP(m, ring_grow(B.ring_dev, gcap * kReducedLen));
     }
   }
   NIDM_HIP(m, hipSetDevice(m->sh[0]->cfg.device));
-  if (m->ring_host_cap < gcap * K) {  // pinned landing zones: kept across calls, grown on demand
-    for (int i = 0; i < kGroupRing; i++) {
-      if (m->ring_host[i]) (void)hipHostFree(m->ring_host[i]);
-      m->ring_host[i] = nullptr;
-      NIDM_HIP(m, hipHostMalloc(reinterpret_cast<void **>(&m->ring_host[i]), gcap * K * kReducedLen * sizeof(double), hipHostMallocDefault));
-    }
-    m->ring_host_cap = gcap * K;
-  }
+  NIDM_HIP(m, ring_grow(m->ring_host, gcap * K * kReducedLen));  // pinned landing zones: kept across calls, grown on demand
   (void)host_blocks;
   for (size_t k = 0; k < K; k++) for (int i = 0; i < kGroupRing; i++) m->buf[k].ring_used[i] = false;
   Pose p[kMaxBatchExt];

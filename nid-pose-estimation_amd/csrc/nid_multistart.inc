@@ -52,50 +52,32 @@ __global__ void __launch_bounds__(64) k_lm_step(const MsStepArgs A) {
   if (A.trace) lm::lm_trace(&S, A.trace + i);
 }
 
-void free_ms_pool(nid_ctx *ctx) {
-  nid_ctx::MsPool &Q = ctx->ms;
-  pool_free(Q.poses);
-  (void)hipFree(Q.reduced); (void)hipFree(Q.state_dev); (void)hipFree(Q.running_dev); (void)hipFree(Q.trace_dev);
-  if (Q.state_host) (void)hipHostFree(Q.state_host);
-  if (Q.running_host) (void)hipHostFree(Q.running_host);
-  Q = nid_ctx::MsPool();
-}
-
-// buffers for `chains` chains and `rounds` rounds (grow only; the trace only when asked for)
+// buffers for `chains` chains and `rounds` rounds (grow only; the trace only when asked for).  A step that fails leaves
+// the count it was growing at zero, and the next call makes that part anew.
 int ensure_ms_pool(nid_ctx *ctx, int chains, int rounds, bool trace) {
   nid_ctx::MsPool &Q = ctx->ms;
   if (Q.chains < chains) {
-    resident_retire(ctx);  // (hipFree waits for the whole device)
-    const int r_keep = Q.rounds;
-    free_ms_pool(ctx);
-    rounds = std::max(rounds, r_keep);
+    resident_retire(ctx);  // (a release waits for the whole device)
+    rounds = std::max(rounds, Q.rounds);
+    Q = nid_ctx::MsPool();
     const size_t n = (size_t)chains;
     int rc;
     if ((rc = pool_ensure(ctx, Q.poses, n, true))) return rc;
-    if ((rc = dev_alloc(ctx, &Q.reduced, n * kReducedLen))) return rc;
-    if ((rc = dev_alloc(ctx, &Q.state_dev, n))) return rc;
-    if (hipHostMalloc(reinterpret_cast<void **>(&Q.state_host), n * sizeof(nid_ms_state), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
+    NID_HIP(ctx, Q.reduced.alloc(n * kReducedLen));
+    NID_HIP(ctx, Q.state_dev.alloc(n));
+    NID_HIP(ctx, Q.state_host.alloc(n));
     Q.chains = chains;
   }
   if (Q.rounds < rounds) {
     resident_retire(ctx);
-    (void)hipFree(Q.running_dev);
-    if (Q.running_host) (void)hipHostFree(Q.running_host);
-    Q.running_dev = Q.running_host = nullptr;
     Q.rounds = 0;
-    int rc;
-    if ((rc = dev_alloc(ctx, &Q.running_dev, (size_t)rounds))) return rc;
-    if (hipHostMalloc(reinterpret_cast<void **>(&Q.running_host), (size_t)rounds * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) return NID_ERR_NOMEM;
+    NID_HIP(ctx, Q.running_dev.alloc((size_t)rounds));
+    NID_HIP(ctx, Q.running_host.alloc((size_t)rounds));
     Q.rounds = rounds;
   }
-  if (trace && Q.trace_cap < (size_t)rounds * chains) {
+  if (trace && Q.trace_dev.size() < (size_t)rounds * chains) {
     resident_retire(ctx);
-    (void)hipFree(Q.trace_dev);
-    Q.trace_dev = nullptr;
-    Q.trace_cap = 0;
-    int rc;
-    if ((rc = dev_alloc(ctx, &Q.trace_dev, (size_t)rounds * chains))) return rc;
-    Q.trace_cap = (size_t)rounds * chains;
+    NID_HIP(ctx, Q.trace_dev.alloc((size_t)rounds * chains));
   }
   return NID_OK;
 }

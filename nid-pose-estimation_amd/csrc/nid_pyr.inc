@@ -12,7 +12,7 @@
 struct nid_pyr {
   int levels = 0;
   nid_ctx *ctx[NID_PYR_MAX_LEVELS] = {};
-  hipEvent_t idle[NID_PYR_MAX_LEVELS][2] = {};  // a level's stream / aux_stream have reached this call
+  Event idle[NID_PYR_MAX_LEVELS][2];  // a level's stream / aux_stream have reached this call
   bool have_pair = false;  // a reference is resident on every level (nid_pyr_set_pair_u16, or a promoted target: nid_pyr_stream.inc)
 };
 
@@ -92,12 +92,8 @@ int nid_pyr_level_config(const nid_config *cfg0, int level, nid_config *out) {
 
 int nid_pyr_destroy(nid_pyr *p) {
   if (!p) return NID_OK;
-  for (int l = 0; l < p->levels; l++) {
-    if (p->ctx[l]) (void)hipSetDevice(p->ctx[l]->cfg.device);
-    for (hipEvent_t e : p->idle[l]) if (e) (void)hipEventDestroy(e);
-    (void)nid_destroy(p->ctx[l]);
-  }
-  delete p;
+  for (int l = 0; l < p->levels; l++) (void)nid_destroy(p->ctx[l]);  // (each selects the device: the one of every level)
+  delete p;  // (the idle events)
   return NID_OK;
 }
 
@@ -117,9 +113,9 @@ int nid_pyr_create(const nid_config *cfg0, int levels, nid_pyr **out) {
     if ((rc = nid_create(&c, &p->ctx[l]))) return fail(rc);
     // (here, not on the first pair: hipMalloc waits for the whole device)
     nid_ctx *ctx = p->ctx[l];
-    if ((rc = dev_alloc(ctx, &ctx->depth16_dev, (size_t)c.rows * c.cols))) return fail(rc);
-    for (hipEvent_t &e : p->idle[l])
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
+    if (ctx->depth16_dev.alloc((size_t)c.rows * c.cols) != hipSuccess) return fail(NID_ERR_NOMEM);
+    for (Event &e : p->idle[l])
+      if (e.create(hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
   }
   *out = p;
   return NID_OK;

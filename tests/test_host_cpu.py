@@ -418,3 +418,25 @@ def test_fused_grid_budget_rule_matches_hand_derived_values(tmp_path):
                            "-o", exe, os.path.join(ROOT, "tests", "cpp", "pose_pool_check.cpp")])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "pose pool rule ok" in r.stdout, r.stdout[-2000:]
+
+
+def test_hip_owner_types_release_once_and_fail_clean(tmp_path):
+    """csrc/nid_hip_owned.h (DevBuf, PinnedBuf, Event, Stream, ring_size / ring_grow: who owns the host layer's device
+    memory, pinned memory, events and streams; only the runtime's API header in it) against tests/cpp/hip_owned_check.cpp's
+    counting fakes of the eleven hip* entry points it calls -- no HIP library is linked: nothing live behind any scope
+    (moved-from and move-assigned objects, vectors and arrays of them); alloc frees first and allocates exactly n, grow
+    within the size makes no HIP call, a mapped buffer whose device-pointer query fails is given back; every creation of a
+    context in miniature failed in turn leaves that owner empty with size 0, the others whole, and no error pending; and a
+    ring of 4 grown to 8, then to 32 with the third allocation refused, then asked for 8, allocates exactly the missing
+    entry (or fails) -- it never reports that its capacity suffices.  A stand-alone program under AddressSanitizer (double
+    release, use after release) + UndefinedBehaviorSanitizer, their runtimes linked statically."""
+    exe = tmp_path / "hip_owned_check"
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-static-libubsan", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(rocm, "include"),
+                           "-I", os.path.join(ROOT, "nid-pose-estimation_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "hip_owned_check.cpp"),
+                           "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
+    m = re.search(r"hip owned: (\d+) fake HIP calls, (\d+) creations, 0 failures", r.stdout)
+    assert m and int(m.group(2)) >= 100, r.stdout

@@ -131,3 +131,58 @@ def test_private_pools_and_public_slots_in_turn(capi, pair_S, one):
         assert got[0].tobytes() == want[0].tobytes() and got[1:3] == want[1:3], f"{n} chains: results, best or rounds differ"
         assert got[3].tobytes() == want[3].tobytes(), f"{n} chains: traces differ"
     fresh.close()
+
+
+def test_growable_buffers_small_large_small(capi, synth, pair_S):
+    """Every buffer that grows with the request -- the pipelined loop's result rings and the fused pool, nid_multistart_lm's
+    pool, round words and trace, nid_multi_run_sequence's rings -- asked for small, then large, then small again on ONE
+    context (one nid_multi of two shards on device 0): every result equals, bit for bit, the same call on a context that
+    has made no other call.  Then everything is closed and a new context is used once: a release that took something
+    still in use would show there."""
+    poses = _poses(synth, pair_S, NPOSES, 23)
+
+    def context():
+        c = capi.from_pair(pair_S, 8)
+        c.compute_href(pair_S.pose_init)
+        return c
+
+    def multi():
+        m = capi.multi_from_pair(pair_S, 8, devices=(0, 0))
+        m.compute_href(pair_S.pose_init)
+        return m
+
+    def fresh(make, call):
+        c = make()
+        try:
+            return call(c)
+        finally:
+            c.close()
+
+    short, long_ = poses[np.arange(12) % NPOSES], poses[np.arange(2 * 64 * 16) % NPOSES]
+    calls = [("run_sequence batch 2", lambda c: c.run_sequence(short, DELTA, batch=2).tobytes()),      # 6 launches, ring of 2
+             ("run_sequence batch 16, fused", lambda c: c.run_sequence(long_, DELTA, batch=16).tobytes()),  # two grids of 1024: rings and pool grow
+             ("run_sequence batch 2 again", lambda c: c.run_sequence(short, DELTA, batch=2).tobytes())]
+
+    def ms(n, iterations, trace):
+        def call(c):
+            got = c.multistart_lm(poses[:n], iterations, DELTA, trace=trace)
+            return (got[0].tobytes(), got[1], got[2]) + ((got[3].tobytes(),) if trace else ())
+        return call
+    calls += [("multistart 2 chains", ms(2, 3, False)), ("multistart 6 chains, traced, more rounds", ms(6, 7, True)),
+              ("multistart 2 chains again", ms(2, 3, False))]
+
+    ctx = context()
+    for what, call in calls:
+        assert call(ctx) == fresh(context, call), what
+    ctx.close()
+
+    seq = poses[np.arange(40) % NPOSES]
+    m = multi()
+    for batch, group in ((2, 2), (4, 4), (2, 2)):  # group * batch 4, 16, 4: the shards' device rings and the pinned landing zones
+        call = lambda c: c.run_sequence(seq, DELTA, batch=batch, group=group).tobytes()
+        assert call(m) == fresh(multi, call), f"multi run_sequence batch {batch} group {group}"
+    m.close()
+
+    again = context()
+    assert _same(again.run_sequence(short, DELTA, batch=2)[:, :29], np.stack([_pack(again.normal_equations(p, DELTA)) for p in short]))
+    again.close()
