@@ -33,7 +33,9 @@
  * call, while the pyramid's target is the new image (or not ready, if the error was nid_pyr_set_target_u8's), and its
  * reference is not ready if the error was the promotion's.
  *
- * Out of scope: cell shards or several devices, keyframe selection policies, an asynchronous push, a host-layer wrapper.
+ * Out of scope: cell shards or several devices, an asynchronous push, a host-layer wrapper.  Keyframe selection policies
+ * and a check of a result against the frame's depth are a header of their own: nid/nid_keyframe.h; without a policy set
+ * there, the tracker is exactly the schedule above.
  */
 #ifndef NID_PYR_STREAM_H
 #define NID_PYR_STREAM_H

@@ -95,6 +95,25 @@ class TrackResult(C.Structure):
 
 assert C.sizeof(TrackResult) == 120
 
+# include/nid/nid_keyframe.h (a header of its own once more: the depth-consistency check and the tracker's keyframe policy)
+KEYFRAME_SYMBOLS = ["nid_pyr_set_target_depth_u16", "nid_pyr_promote_target", "nid_pyr_depth_check", "nid_depth_check_host",
+                    "nid_track_policy_default", "nid_track_set_policy", "nid_track_last_check"]
+TRACK_REJECTED = 3
+# nid_depth_cell / nid_depth_counts as numpy records (tobytes() of two arrays compares every bit)
+DEPTH_CELL_DTYPE = np.dtype([("n_ref", "i4"), ("n_inframe", "i4"), ("n_both", "i4"), ("n_consistent", "i4"), ("n_occluded", "i4"),
+                             ("n_through", "i4"), ("sum_abs_um", "u8")])
+DEPTH_COUNTS_DTYPE = np.dtype([("n_ref", "i8"), ("n_inframe", "i8"), ("n_both", "i8"), ("n_consistent", "i8"), ("n_occluded", "i8"),
+                               ("n_through", "i8"), ("sum_abs_um", "u8"), ("reserved", "u8")])
+
+
+class TrackPolicy(C.Structure):
+    """nid_track_policy"""
+    _fields_ = [("keyframe_mode", C.c_int32), ("max_age", C.c_int32), ("min_samples", C.c_int32), ("reserved", C.c_int32),
+                ("min_overlap", C.c_double), ("min_consistent", C.c_double), ("tol_abs", C.c_double), ("tol_rel", C.c_double)]
+
+
+assert DEPTH_CELL_DTYPE.itemsize == 32 and DEPTH_COUNTS_DTYPE.itemsize == 64 and C.sizeof(TrackPolicy) == 48
+
 _lib = None
 
 
@@ -209,6 +228,15 @@ def load():
         lib.nid_track_set_twists.argtypes = [vp, c_dp, C.c_int]
         lib.nid_track_set_pose.argtypes = [vp, c_dp]
         lib.nid_track_push_u16.argtypes = [vp, u16p, C.c_double, c_u8p, c_dp, C.POINTER(TrackResult)]
+    if hasattr(lib, "nid_pyr_depth_check"):   # (likewise)
+        u16p = C.POINTER(C.c_uint16)
+        lib.nid_pyr_set_target_depth_u16.argtypes = [vp, u16p, C.c_double]
+        lib.nid_pyr_promote_target.argtypes = [vp, c_dp]
+        lib.nid_pyr_depth_check.argtypes = [vp, c_dp, C.c_int, C.c_double, C.c_double, vp, vp]
+        lib.nid_depth_check_host.argtypes = [C.POINTER(NidConfig), c_dp, u16p, C.c_double, c_dp, C.c_double, C.c_double, vp, vp]
+        lib.nid_track_policy_default.argtypes = [C.POINTER(TrackPolicy)]
+        lib.nid_track_set_policy.argtypes = [vp, C.POINTER(TrackPolicy)]
+        lib.nid_track_last_check.argtypes = [vp, vp, c_ip, c_ip]
     _lib = lib
     return lib
 
@@ -702,6 +730,30 @@ class Pyramid:
         self._check(self.lib.nid_pyr_promote_target_u16(self.h, d.ctypes.data_as(C.POINTER(C.c_uint16)), float(depth_factor), _dp(T)),
                     "nid_pyr_promote_target_u16")
 
+    def set_target_depth(self, depth_u16, depth_factor=1.0 / 5000):
+        """nid_pyr_set_target_depth_u16: the resident target's depth map, kept at level 0 (nid_keyframe.h)."""
+        d = np.ascontiguousarray(depth_u16, dtype=np.uint16).reshape(-1)
+        assert d.size == self.cfg0.rows * self.cfg0.cols
+        self._check(self.lib.nid_pyr_set_target_depth_u16(self.h, d.ctypes.data_as(C.POINTER(C.c_uint16)), float(depth_factor)),
+                    "nid_pyr_set_target_depth_u16")
+
+    def promote_resident_target(self, T_wc_colmajor16):
+        """nid_pyr_promote_target: promote_target with the resident target depth, copied on the device."""
+        T = _d(T_wc_colmajor16)
+        assert T.size == 16
+        self._check(self.lib.nid_pyr_promote_target(self.h, _dp(T)), "nid_pyr_promote_target")
+
+    def depth_check(self, poses, tol_abs=0.01, tol_rel=0.02, cells=True):
+        """nid_pyr_depth_check: (totals [n] DEPTH_COUNTS_DTYPE, cells [n, cells of level 0] DEPTH_CELL_DTYPE or None)."""
+        p = _d(np.asarray(poses).reshape(-1, 7))
+        n = p.shape[0]
+        ncell = self.cfg0.cell_num * self.cfg0.cell_num
+        tot = np.zeros(max(n, 1), dtype=DEPTH_COUNTS_DTYPE)
+        cel = np.zeros((max(n, 1), ncell), dtype=DEPTH_CELL_DTYPE) if cells else None
+        self._check(self.lib.nid_pyr_depth_check(self.h, _dp(p), n, float(tol_abs), float(tol_rel), tot.ctypes.data_as(C.c_void_p),
+                                                 cel.ctypes.data_as(C.c_void_p) if cells else None), "nid_pyr_depth_check")
+        return tot[:n], (cel[:n] if cells else None)
+
     def get_level_inputs(self, level):
         """(depth_u16, im0, im1) of a level as the device holds them."""
         c = self.level_config(level)
@@ -837,6 +889,17 @@ class Tracker:
         assert p.size == 7
         self._check(self.lib.nid_track_set_pose(self.h, _dp(p)), "nid_track_set_pose")
 
+    def set_policy(self, policy):
+        """nid_track_set_policy (a TrackPolicy, e.g. track_policy_default() with members changed)"""
+        self._check(self.lib.nid_track_set_policy(self.h, C.byref(policy)), "nid_track_set_policy")
+
+    def last_check(self):
+        """nid_track_last_check: (chosen candidate's counts as a DEPTH_COUNTS_DTYPE record, poses checked, age)"""
+        chosen = np.zeros(1, dtype=DEPTH_COUNTS_DTYPE)
+        n, age = C.c_int32(-1), C.c_int32(-1)
+        self._check(self.lib.nid_track_last_check(self.h, chosen.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(age)), "nid_track_last_check")
+        return chosen[0], int(n.value), int(age.value)
+
     def push(self, im, depth_u16=None, depth_factor=1.0 / 5000, T_wc_first=None):
         """nid_track_push_u16: one frame.  Returns a dict of nid_track_result's members (pose7 and rounds as arrays)."""
         N = self.cfg0.rows * self.cfg0.cols
@@ -850,6 +913,34 @@ class Tracker:
         return dict(pose7=np.array(r.pose7[:]), chi2=float(r.chi2), n_active=int(r.n_active), best_origin=int(r.best_origin),
                     status=int(r.status), promoted=int(r.promoted), frame=int(r.frame),
                     rounds=np.array(r.rounds[:self.levels], dtype=np.int32))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# include/nid/nid_keyframe.h: the host build of the depth-consistency check (no device) and the default policy
+def track_policy_default():
+    lib = load()
+    pol = TrackPolicy()
+    rc = lib.nid_track_policy_default(C.byref(pol))
+    if rc != NID_OK:
+        raise NidError(f"nid_track_policy_default: {rc}")
+    return pol
+
+
+def depth_check_host(cfg, points3d, depth1_u16, depth_factor, pose7, tol_abs=0.01, tol_rel=0.02):
+    """nid_depth_check_host over nid_get_points3d's layout: (total as a DEPTH_COUNTS_DTYPE record, cells [cell_num^2]
+    DEPTH_CELL_DTYPE) -- what k_depth_check computes, from the same text compiled for the host."""
+    lib = load()
+    pts = _d(points3d).reshape(-1)
+    d = np.ascontiguousarray(depth1_u16, dtype=np.uint16).reshape(-1)
+    q = _d(pose7)
+    assert pts.size == 3 * cfg.rows * cfg.cols and d.size == cfg.rows * cfg.cols and q.size == 7
+    tot = np.zeros(1, dtype=DEPTH_COUNTS_DTYPE)
+    cel = np.zeros(cfg.cell_num * cfg.cell_num, dtype=DEPTH_CELL_DTYPE)
+    rc = lib.nid_depth_check_host(C.byref(cfg), _dp(pts), d.ctypes.data_as(C.POINTER(C.c_uint16)), float(depth_factor), _dp(q),
+                                  float(tol_abs), float(tol_rel), tot.ctypes.data_as(C.c_void_p), cel.ctypes.data_as(C.c_void_p))
+    if rc != NID_OK:
+        raise NidError(f"nid_depth_check_host: {lib.nid_status_string(rc).decode()} ({rc})")
+    return tot[0], cel
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -24,13 +24,15 @@
 #include "nid/nid_multistart.h"
 #include "nid/nid_pyr.h"
 #include "nid/nid_pyr_stream.h"
+#include "nid/nid_keyframe.h"
 #include "nid_eval_launch.h"
 #include "nid_hip_owned.h"            // DevBuf, PinnedBuf, Event, Stream: who owns the device memory, pinned memory, events and streams (no kernels in it)
 #include "nid_pose_pool.h"             // pose_sizes, seq_fusion: per-pose buffer sizes and the fused grids' budget rule (no HIP in it)
 #include "nid_direct_sum.h"            // DirectSum, add_block: the host's arithmetic and order of a DIRECT / GROUP-DIRECT launch (no HIP in it)
 #include "nid_lm_step.h"               // lm_step: the per-chain rule of nid_multistart_lm, compiled here for the device and the host
 #include "nid_track_pose.h"            // pose inverse / compose / perturb of nid_pyr_stream.h, on nid_lm_step.h's SE(3) text (no HIP in it)
-#include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_pyr_down (+ _u8, _depth), k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
+#include "nid_depth_check.h"           // dc::sample and the tracker's two decisions of nid_keyframe.h, compiled here for the device and the host (no HIP in it)
+#include "nid_setup_kernels.hip.h"     // k_tile, k_im1_margins, k_pyr_down (+ _u8, _depth), k_depth_check, k_backproject_plain, k_href, k_plain_nid, k_untile_bs: this translation unit's
 #include "nid_resident_kernels.hip.h"  // control words and record layouts of the resident evaluators (their kernels: nid_resident_tu.hip)
 
 using namespace nid;
@@ -2150,3 +2152,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- frame streams on the resident pyramid: a new target alone, target -> reference, a tracker (include/nid/nid_pyr_stream.h) ---
 #include "nid_pyr_stream.inc"
+
+// ---- the depth-consistency check on the resident pyramid and the tracker's keyframe policy (include/nid/nid_keyframe.h) ---
+#include "nid_keyframe.inc"

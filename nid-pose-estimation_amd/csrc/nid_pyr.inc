@@ -14,6 +14,18 @@ struct nid_pyr {
   nid_ctx *ctx[NID_PYR_MAX_LEVELS] = {};
   Event idle[NID_PYR_MAX_LEVELS][2];  // a level's stream / aux_stream have reached this call
   bool have_pair = false;  // a reference is resident on every level (nid_pyr_set_pair_u16, or a promoted target: nid_pyr_stream.inc)
+  // nid_keyframe.inc: the resident target's depth at level 0 (made with the pyramid), and the depth check's buffers
+  // (made on its first call): the poses' matrices and the totals through one pinned block, the cell records
+  DevBuf<uint16_t> tdepth_dev;
+  bool have_tdepth = false;  // cleared by whatever replaces the target
+  double tdepth_factor = 0;
+  struct DepthCheck {
+    DevBuf<double> M_dev;                    // [NID_MAX_BATCH][12]
+    DevBuf<unsigned long long> totals_dev;   // [NID_MAX_BATCH][8]
+    DevBuf<nid_depth_cell> cells_dev;        // [NID_MAX_BATCH][cells of level 0]
+    PinnedBuf<unsigned long long> stage;     // the matrices (as doubles), then the totals
+    PinnedBuf<nid_depth_cell> cells_host;    // grown to what a call with cells != NULL asks for
+  } dc;
 };
 
 namespace {
@@ -117,6 +129,7 @@ int nid_pyr_create(const nid_config *cfg0, int levels, nid_pyr **out) {
     for (Event &e : p->idle[l])
       if (e.create(hipEventDisableTiming) != hipSuccess) return fail(NID_ERR_HIP);
   }
+  if (p->tdepth_dev.alloc((size_t)cfg0->rows * cfg0->cols) != hipSuccess) return fail(NID_ERR_NOMEM);
   *out = p;
   return NID_OK;
 }
@@ -131,7 +144,7 @@ int nid_pyr_set_pair_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_fac
   int rc = pyr_refuse_pending(p, "nid_pyr_set_pair_u16");
   if (rc) return rc;
   // from here on the levels are being overwritten: none of them is ready until the stream has drained
-  p->have_pair = false;
+  p->have_pair = p->have_tdepth = false;
   for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_target = p->ctx[l]->have_href = false;
   if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];

@@ -21,7 +21,64 @@ struct nid_track {
   int32_t frame = 0;  // pushes that returned NID_OK
   std::vector<nid_ms_result> results;
   std::vector<int32_t> origin;
+  // nid_keyframe.h (nid_keyframe.inc): the policy, the frames tracked OK on the keyframe, and what the last push checked
+  nid_track_policy policy = {0, 0, 0, 0, 0.0, 0.0, 0.01, 0.02};
+  int32_t age = 0, n_checked = 0;
+  nid_depth_counts chosen = {};
 };
+
+namespace {
+
+// A later frame with depth under an active policy (nid_keyframe.inc, behind this file): steps 5a - 5d of nid_keyframe.h
+// on the chains nid_pyr_multistart_lm left in t->results / t->origin.  It moves cur / prev as nid_track_push_u16 does, behind
+// its last call that can fail; the age and the last check's record are nid_track_push_u16's to keep.
+int track_finish_with_policy(nid_track *t, int n, nid_track_result *R, nid_depth_counts *chosen, int32_t *n_checked);
+
+// The REFERENCE half for nid_pyr_promote_target_u16 (depth_u16: the caller's map, uploaded) and nid_pyr_promote_target
+// (depth_u16 == NULL: the resident target depth, copied on the device); `what` names the call in an error.
+int pyr_promote(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, const double *Twc, const char *what) {
+  for (int l = 0; l < p->levels; l++)
+    if (!p->ctx[l]->have_target) return pyr_fail(p, NID_ERR_STATE, std::string(what) + ": no target on level " + std::to_string(l));
+  if (!depth_u16 && !p->have_tdepth) return pyr_fail(p, NID_ERR_STATE, std::string(what) + ": the target has no depth: nid_pyr_set_target_depth_u16() first");
+  int rc = pyr_refuse_pending(p, what);
+  if (rc) return rc;
+  // from here on the reference is being overwritten: no level has one until the stream has drained
+  p->have_pair = false;
+  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_href = false;
+  if ((rc = pyr_front(p))) return rc;
+  nid_ctx *c0 = p->ctx[0];
+  const hipStream_t st = c0->stream;
+  if ((rc = pair_stage_ensure(c0))) return rc;  // (nothing enqueued yet)
+  const PairStage L0 = pair_stage_layout(c0->g);
+  const size_t N = (size_t)c0->g.rows * c0->g.cols;
+  if (depth_u16) std::memcpy(c0->pair_stage + L0.depth, depth_u16, 2 * N);
+  std::memcpy(c0->pair_stage + L0.twc, Twc, 16 * sizeof(double));
+  auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) { return hipMemcpyAsync(dst, src, bytes, kind, st) == hipSuccess; };
+  bool ok = depth_u16 ? copy(c0->depth16_dev, c0->pair_stage + L0.depth, 2 * N, hipMemcpyHostToDevice)
+                      : copy(c0->depth16_dev, p->tdepth_dev, 2 * N, hipMemcpyDeviceToDevice);
+  for (int l = 0; ok && l < p->levels; l++) {
+    nid_ctx *ctx = p->ctx[l];
+    ok = copy(ctx->im0_dev, ctx->im1_dev, (size_t)ctx->g.rows * ctx->g.cols, hipMemcpyDeviceToDevice) &&
+         copy(ctx->Twc_dev, c0->pair_stage + L0.twc, 16 * sizeof(double), hipMemcpyHostToDevice);
+  }
+  if (!ok) return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, std::string(what) + ": hipMemcpyAsync"));
+  for (int l = 1; l < p->levels; l++) {
+    nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
+    hipLaunchKernelGGL(k_pyr_down_depth, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->depth16_dev, depth_factor,
+                       dst->depth16_dev);
+  }
+  for (int l = 0; l < p->levels; l++) pair_u16_device_ref(p->ctx[l], depth_factor, st);
+  if ((rc = pyr_finish(p, what))) return rc;
+  for (int l = 0; l < p->levels; l++) {
+    nid_ctx *ctx = p->ctx[l];
+    ctx->have_ref = true;  // (have_href stays false: the reference stage is the caller's)
+    ctx->ref_from_depth = true;
+  }
+  p->have_pair = true;
+  return NID_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -31,6 +88,7 @@ int nid_pyr_set_target_u8(nid_pyr *p, const uint8_t *im1) {
   if (rc) return rc;
   // from here on the target is being overwritten: no level has one until the stream has drained
   for (int l = 0; l < p->levels; l++) p->ctx[l]->have_target = false;
+  p->have_tdepth = false;  // (nid_keyframe.h: a target's depth belongs to its image)
   if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
   const hipStream_t st = c0->stream;
@@ -52,43 +110,7 @@ int nid_pyr_set_target_u8(nid_pyr *p, const uint8_t *im1) {
 
 int nid_pyr_promote_target_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, const double *Twc) {
   if (!p || !depth_u16 || !Twc) return NID_ERR_INVALID_ARG;
-  for (int l = 0; l < p->levels; l++)
-    if (!p->ctx[l]->have_target) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_promote_target_u16: no target on level " + std::to_string(l));
-  int rc = pyr_refuse_pending(p, "nid_pyr_promote_target_u16");
-  if (rc) return rc;
-  // from here on the reference is being overwritten: no level has one until the stream has drained
-  p->have_pair = false;
-  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_href = false;
-  if ((rc = pyr_front(p))) return rc;
-  nid_ctx *c0 = p->ctx[0];
-  const hipStream_t st = c0->stream;
-  if ((rc = pair_stage_ensure(c0))) return rc;  // (nothing enqueued yet)
-  const PairStage L0 = pair_stage_layout(c0->g);
-  const size_t N = (size_t)c0->g.rows * c0->g.cols;
-  std::memcpy(c0->pair_stage + L0.depth, depth_u16, 2 * N);
-  std::memcpy(c0->pair_stage + L0.twc, Twc, 16 * sizeof(double));
-  auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) { return hipMemcpyAsync(dst, src, bytes, kind, st) == hipSuccess; };
-  bool ok = copy(c0->depth16_dev, c0->pair_stage + L0.depth, 2 * N, hipMemcpyHostToDevice);
-  for (int l = 0; ok && l < p->levels; l++) {
-    nid_ctx *ctx = p->ctx[l];
-    ok = copy(ctx->im0_dev, ctx->im1_dev, (size_t)ctx->g.rows * ctx->g.cols, hipMemcpyDeviceToDevice) &&
-         copy(ctx->Twc_dev, c0->pair_stage + L0.twc, 16 * sizeof(double), hipMemcpyHostToDevice);
-  }
-  if (!ok) return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, "nid_pyr_promote_target_u16: hipMemcpyAsync"));
-  for (int l = 1; l < p->levels; l++) {
-    nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
-    hipLaunchKernelGGL(k_pyr_down_depth, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->depth16_dev, depth_factor,
-                       dst->depth16_dev);
-  }
-  for (int l = 0; l < p->levels; l++) pair_u16_device_ref(p->ctx[l], depth_factor, st);
-  if ((rc = pyr_finish(p, "nid_pyr_promote_target_u16"))) return rc;
-  for (int l = 0; l < p->levels; l++) {
-    nid_ctx *ctx = p->ctx[l];
-    ctx->have_ref = true;  // (have_href stays false: the reference stage is the caller's)
-    ctx->ref_from_depth = true;
-  }
-  p->have_pair = true;
-  return NID_OK;
+  return pyr_promote(p, depth_u16, depth_factor, Twc, "nid_pyr_promote_target_u16");
 }
 
 // ---- pose helpers (csrc/nid_track_pose.h) ---------------------------------------------------------------------------
@@ -178,6 +200,8 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   nid_track_result R = {};
   R.best_origin = -1;
   R.frame = t->frame;
+  nid_depth_counts chosen = {};  // (nid_keyframe.h: what this push checked, kept with the poses when it returns NID_OK)
+  int32_t n_checked = 0;
   int rc = nid_pyr_set_target_u8(p, im);
   if (rc) return rc;
   if (first) {
@@ -206,11 +230,16 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
     t->origin.resize((size_t)L * n);
     int best = -1;
     double best_pose[7];
+    // (nid_keyframe.h: an active policy and a frame with depth -- the depth stays on the device for the check and the promotion)
+    const bool with_policy = depth_u16 && dc::policy_active(t->policy);
+    if (with_policy && (rc = nid_pyr_set_target_depth_u16(p, depth_u16, depth_factor))) return rc;
     if ((rc = nid_pyr_multistart_lm(p, starts, n, nullptr, t->iterations, t->delta, t->have_keep ? t->keep : nullptr, t->results.data(),
                                     t->origin.data(), R.rounds, &best, best_pose)))
       return rc;
     R.best_origin = best;
-    if (best >= 0) {
+    if (with_policy && best >= 0) {
+      if ((rc = track_finish_with_policy(t, n, &R, &chosen, &n_checked))) return rc;
+    } else if (best >= 0) {
       if (depth_u16) {
         double Twc[16];
         track::pose_to_Twc16(best_pose, Twc);
@@ -231,6 +260,10 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
     }
   }
   std::memcpy(R.pose7, t->cur, sizeof(t->cur));
+  if (R.promoted) t->age = 0;  // frames tracked OK on the keyframe since it was promoted
+  else if (R.status == NID_TRACK_OK) t->age++;
+  t->chosen = chosen;
+  t->n_checked = n_checked;
   t->frame++;
   *out = R;
   return NID_OK;

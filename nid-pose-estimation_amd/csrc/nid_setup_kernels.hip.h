@@ -1,9 +1,11 @@
 // nid_setup_kernels.hip.h -- the once-per-pair kernels: back-projection + tiling, the target image's margins, the reference
 // stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
-// next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth).
+// next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth), the depth-consistency check of the
+// keyframe's points against the target's depth (k_depth_check).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
+#include "nid_depth_check.h"
 #include "nid_kernels.hip.h"
 
 namespace nid {
@@ -200,6 +202,59 @@ __global__ void __launch_bounds__(256) k_pyr_down_depth(int rows2, int cols2, co
       const uint16_t v[4] = {depth[s], depth[s + 1], depth[s + cols], depth[s + cols + 1]};
       o_depth[out + k] = pyr_depth_mean(v, factor);
     }
+  }
+}
+
+// The depth-consistency check (nid/nid_keyframe.h): ONE workgroup per (cell, pose), pose-major -- with a cell count that is
+// a multiple of the XCDs, a cell's tile is read by one XCD for every pose and can stay in its L2 --, 256 lanes striding over
+// the cell's pstride slots (a multiple of 64, not of 256: the loop is bounded on the slot).  X / Y / Z are coalesced f64
+// reads, the u16 depth gather stays inside the cell's footprint moved by the pose.  Each lane runs dc::sample
+// (nid_depth_check.h: the host's text) into six 32-bit counts and one 64-bit sum; the wave sums them with shuffles, the
+// four waves meet in LDS, lanes 0 .. 6 write the cell's 32-byte record with plain stores and add their sum to the pose's
+// totals with ONE 64-bit INTEGER atomic each (exact and order-independent: no float is summed anywhere).
+struct DepthCheckArgs {
+  const double *M;              // [n][12]: rows of [R|t] per pose (lm::pose_record)
+  const uint16_t *d1;           // level 0's target depth, rows x cols
+  double factor, tol_abs, tol_rel;
+  nid_depth_cell *cells;        // [n][nloc]
+  unsigned long long *totals;   // [n][8]: nid_depth_counts, zero before the launch
+};
+static_assert(sizeof(nid_depth_cell) == 32 && sizeof(nid_depth_counts) == 64, "nid_keyframe.h's records");
+static_assert(offsetof(nid_depth_cell, n_through) == 20 && offsetof(nid_depth_cell, sum_abs_um) == 24, "six counts, then the sum");
+static_assert(offsetof(nid_depth_counts, sum_abs_um) == 48, "a total is the cell record's members widened, in its order");
+
+__global__ void __launch_bounds__(256) k_depth_check(Geometry g, Tiles t, DepthCheckArgs A) {
+  __shared__ unsigned long long part[4][8];
+  const int cl = (int)(blockIdx.x % (unsigned)g.nloc), pose = (int)(blockIdx.x / (unsigned)g.nloc), tid = threadIdx.x;
+  dc::View V;
+#pragma unroll
+  for (int k = 0; k < 12; k++) V.M[k] = A.M[(size_t)pose * 12 + k];
+  V.fx = g.fx; V.fy = g.fy; V.cx = g.cx; V.cy = g.cy;
+  V.rows = g.rows; V.cols = g.cols;
+  V.d1 = A.d1; V.factor = A.factor; V.tol_abs = A.tol_abs; V.tol_rel = A.tol_rel;
+  nid_depth_cell a = {};
+  const size_t base = (size_t)cl * g.pstride;
+  for (int s = tid; s < g.pstride; s += 256) dc::sample(V, t.X[base + s], t.Y[base + s], t.Z[base + s], &a);
+  int cnt[6] = {a.n_ref, a.n_inframe, a.n_both, a.n_consistent, a.n_occluded, a.n_through};
+  unsigned long long um = a.sum_abs_um;
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) cnt[k] += __shfl_down(cnt[k], o, 64);
+    um += __shfl_down(um, o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) part[tid >> 6][k] = (unsigned long long)cnt[k];
+    part[tid >> 6][6] = um;
+  }
+  __syncthreads();
+  if (tid < 7) {
+    const unsigned long long s = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+    nid_depth_cell *out = A.cells + ((size_t)pose * g.nloc + cl);
+    if (tid < 6) reinterpret_cast<int32_t *>(out)[tid] = (int32_t)s;
+    else out->sum_abs_um = s;
+    atomicAdd(A.totals + (size_t)pose * 8 + tid, s);
   }
 }
 
