@@ -41,8 +41,9 @@
  *         age >= max_age).  A promotion is nid_pyr_promote_target(nid_track_pose_to_Twc16(cur)) and sets age = 0.
  * age is 0 after the first frame.  Errors of composed calls are returned as they are, as in nid_pyr_stream.h.
  *
- * Out of scope: cell shards and several devices, a target depth on the coarser levels, per-pixel masks fed back into
- * the evaluation, a host-layer wrapper, an asynchronous push.
+ * Out of scope: cell shards and several devices, a target depth on the coarser levels, a host-layer wrapper, an
+ * asynchronous push.  Per-pixel masks on the reference, fed back into the evaluation, are nid_refmask.h, which lists
+ * masks on the target, shards and masks on several devices as out of scope.
  */
 #ifndef NID_KEYFRAME_H
 #define NID_KEYFRAME_H

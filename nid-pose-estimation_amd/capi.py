@@ -114,6 +114,15 @@ class TrackPolicy(C.Structure):
 
 assert DEPTH_CELL_DTYPE.itemsize == 32 and DEPTH_COUNTS_DTYPE.itemsize == 64 and C.sizeof(TrackPolicy) == 48
 
+# include/nid/nid_refmask.h (a header of its own again: a per-pixel mask on the pyramid's reference, the tracker's use of it)
+REFMASK_SYMBOLS = ["nid_pyr_set_reference_mask_u8", "nid_pyr_mask_occluded", "nid_pyr_clear_reference_mask",
+                   "nid_pyr_get_reference_mask_u8", "nid_refmask_host", "nid_track_set_masking", "nid_track_last_mask"]
+REFMASK_CALLER, REFMASK_OCCLUDED, REFMASK_THROUGH, REFMASK_DILATED = 1, 2, 4, 8
+REFMASK_MAX_DILATE = 8
+REFMASK_COUNTS_DTYPE = np.dtype([("n_valid", "i8"), ("n_caller", "i8"), ("n_occluded", "i8"), ("n_through", "i8"), ("n_dilated", "i8"),
+                                 ("n_masked", "i8"), ("reserved", "i8", 2)])
+assert REFMASK_COUNTS_DTYPE.itemsize == 64
+
 _lib = None
 
 
@@ -237,6 +246,16 @@ def load():
         lib.nid_track_policy_default.argtypes = [C.POINTER(TrackPolicy)]
         lib.nid_track_set_policy.argtypes = [vp, C.POINTER(TrackPolicy)]
         lib.nid_track_last_check.argtypes = [vp, vp, c_ip, c_ip]
+    if hasattr(lib, "nid_pyr_mask_occluded"):   # (likewise)
+        u16p = C.POINTER(C.c_uint16)
+        lib.nid_pyr_set_reference_mask_u8.argtypes = [vp, c_u8p]
+        lib.nid_pyr_mask_occluded.argtypes = [vp, c_dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, vp]
+        lib.nid_pyr_clear_reference_mask.argtypes = [vp]
+        lib.nid_pyr_get_reference_mask_u8.argtypes = [vp, c_u8p]
+        lib.nid_refmask_host.argtypes = [C.POINTER(NidConfig), u16p, C.c_double, c_dp, u16p, C.c_double, c_dp, C.c_double, C.c_double,
+                                         C.c_int, C.c_int, C.c_int, c_u8p, vp]
+        lib.nid_track_set_masking.argtypes = [vp, C.c_int, C.c_int]
+        lib.nid_track_last_mask.argtypes = [vp, vp]
     _lib = lib
     return lib
 
@@ -754,6 +773,30 @@ class Pyramid:
                                                  cel.ctypes.data_as(C.c_void_p) if cells else None), "nid_pyr_depth_check")
         return tot[:n], (cel[:n] if cells else None)
 
+    def set_reference_mask(self, mask):
+        """nid_pyr_set_reference_mask_u8: the caller's bit from mask != 0, the derived bits cleared, the reference rebuilt."""
+        m = _u8(mask).reshape(-1)
+        assert m.size == self.cfg0.rows * self.cfg0.cols
+        self._check(self.lib.nid_pyr_set_reference_mask_u8(self.h, m.ctypes.data_as(c_u8p)), "nid_pyr_set_reference_mask_u8")
+
+    def mask_occluded(self, pose7, tol_abs=0.01, tol_rel=0.02, classes=REFMASK_OCCLUDED | REFMASK_THROUGH, dilate=0, accumulate=False):
+        """nid_pyr_mask_occluded: the counts as a REFMASK_COUNTS_DTYPE record."""
+        q = _d(pose7)
+        assert q.size == 7
+        n = np.zeros(1, dtype=REFMASK_COUNTS_DTYPE)
+        self._check(self.lib.nid_pyr_mask_occluded(self.h, _dp(q), float(tol_abs), float(tol_rel), int(classes), int(dilate), int(accumulate),
+                                                   n.ctypes.data_as(C.c_void_p)), "nid_pyr_mask_occluded")
+        return n[0]
+
+    def clear_reference_mask(self):
+        self._check(self.lib.nid_pyr_clear_reference_mask(self.h), "nid_pyr_clear_reference_mask")
+
+    def get_reference_mask(self):
+        """nid_pyr_get_reference_mask_u8: the plane (rows x cols of level 0) as the device holds it."""
+        m = np.zeros((self.cfg0.rows, self.cfg0.cols), dtype=np.uint8)
+        self._check(self.lib.nid_pyr_get_reference_mask_u8(self.h, m.ctypes.data_as(c_u8p)), "nid_pyr_get_reference_mask_u8")
+        return m
+
     def get_level_inputs(self, level):
         """(depth_u16, im0, im1) of a level as the device holds them."""
         c = self.level_config(level)
@@ -900,6 +943,16 @@ class Tracker:
         self._check(self.lib.nid_track_last_check(self.h, chosen.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(age)), "nid_track_last_check")
         return chosen[0], int(n.value), int(age.value)
 
+    def set_masking(self, classes, dilate=0):
+        """nid_track_set_masking (nid_refmask.h): classes 0 is off"""
+        self._check(self.lib.nid_track_set_masking(self.h, int(classes), int(dilate)), "nid_track_set_masking")
+
+    def last_mask(self):
+        """nid_track_last_mask: the counts of the last push's step 5e as a REFMASK_COUNTS_DTYPE record (zeros: it ran none)"""
+        n = np.zeros(1, dtype=REFMASK_COUNTS_DTYPE)
+        self._check(self.lib.nid_track_last_mask(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_mask")
+        return n[0]
+
     def push(self, im, depth_u16=None, depth_factor=1.0 / 5000, T_wc_first=None):
         """nid_track_push_u16: one frame.  Returns a dict of nid_track_result's members (pose7 and rounds as arrays)."""
         N = self.cfg0.rows * self.cfg0.cols
@@ -941,6 +994,27 @@ def depth_check_host(cfg, points3d, depth1_u16, depth_factor, pose7, tol_abs=0.0
     if rc != NID_OK:
         raise NidError(f"nid_depth_check_host: {lib.nid_status_string(rc).decode()} ({rc})")
     return tot[0], cel
+
+
+def refmask_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1, pose7, tol_abs=0.01, tol_rel=0.02,
+                 classes=REFMASK_OCCLUDED | REFMASK_THROUGH, dilate=0, accumulate=False, mask=None):
+    """nid_refmask_host (nid_refmask.h): one call of the rule on a copy of `mask` (None: zeros): (plane [rows, cols] u8,
+    counts as a REFMASK_COUNTS_DTYPE record) -- what nid_pyr_mask_occluded computes, from the same text compiled for the host."""
+    lib = load()
+    N = cfg.rows * cfg.cols
+    u16p = C.POINTER(C.c_uint16)
+    d0 = np.ascontiguousarray(depth0_u16, dtype=np.uint16).reshape(-1)
+    d1 = np.ascontiguousarray(depth1_u16, dtype=np.uint16).reshape(-1)
+    T, q = _d(T_wc_colmajor16), _d(pose7)
+    m = np.zeros(N, dtype=np.uint8) if mask is None else np.array(mask, dtype=np.uint8).reshape(-1)
+    assert d0.size == N and d1.size == N and m.size == N and T.size == 16 and q.size == 7
+    n = np.zeros(1, dtype=REFMASK_COUNTS_DTYPE)
+    rc = lib.nid_refmask_host(C.byref(cfg), d0.ctypes.data_as(u16p), float(factor0), _dp(T), d1.ctypes.data_as(u16p), float(factor1), _dp(q),
+                              float(tol_abs), float(tol_rel), int(classes), int(dilate), int(accumulate), m.ctypes.data_as(c_u8p),
+                              n.ctypes.data_as(C.c_void_p))
+    if rc != NID_OK:
+        raise NidError(f"nid_refmask_host: {lib.nid_status_string(rc).decode()} ({rc})")
+    return m.reshape(cfg.rows, cfg.cols), n[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------

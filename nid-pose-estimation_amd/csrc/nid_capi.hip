@@ -2155,3 +2155,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- the depth-consistency check on the resident pyramid and the tracker's keyframe policy (include/nid/nid_keyframe.h) ---
 #include "nid_keyframe.inc"
+
+// ---- a per-pixel mask on the resident pyramid's reference and the tracker's use of it (include/nid/nid_refmask.h) ---
+#include "nid_refmask.inc"

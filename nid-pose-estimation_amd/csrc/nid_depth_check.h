@@ -1,6 +1,9 @@
 // nid_depth_check.h -- the per-sample rule of the depth-consistency check and the tracker's two decisions
 // (include/nid/nid_keyframe.h): the ONE definition the device (k_depth_check in nid_setup_kernels.hip.h) and the host
-// (nid_depth_check_host; the tracker in nid_keyframe.inc) are compiled from.
+// (nid_depth_check_host; the tracker in nid_keyframe.inc) are compiled from.  Behind them the rule of the reference mask
+// (include/nid/nid_refmask.h) on the same terms: the set-up's back-projection (k_tile calls it), a pixel's byte from its
+// class, the dilation's outcome and the counts -- k_refmask_classify / k_refmask_dilate_apply on the device,
+// dc::refmask_host (nid_refmask_host) on the host.
 //
 // Bitwise agreement of the two compilations: IEEE + - * / on doubles, comparisons, floor and integer arithmetic; both
 // sides are compiled with -ffp-contract=off and without fast-math.  Every result is an integer, so neither the order of
@@ -11,6 +14,7 @@
 #include <stdint.h>
 
 #include "nid/nid_keyframe.h"
+#include "nid/nid_refmask.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define NID_DC_HD __host__ __device__ inline
@@ -32,28 +36,51 @@ struct View {
   double factor, tol_abs, tol_rel;
 };
 
-// One reference sample into the running counts `a` (steps 1 - 5 of nid_keyframe.h).
-NID_DC_HD void sample(const View &V, double X, double Y, double Z, nid_depth_cell *a) {
-  if (X != X) return;  // 1. no reference sample
-  a->n_ref++;
+// The class of one reference sample (steps 1 - 5 of nid_keyframe.h), in the order the steps decide it
+enum Class : int {
+  kNone = 0,           // 1. no reference sample
+  kNotInView = 1,      // 2. / 3. behind the camera or out of the frame
+  kNoTargetDepth = 2,  // 4. the target's depth there is not valid
+  kConsistent = 3,     // 5.
+  kOccluded = 4,
+  kThrough = 5
+};
+
+// THE RULE for one sample; *dz (may be null) is zc - zt of a sample that reached step 5
+NID_DC_HD Class classify(const View &V, double X, double Y, double Z, double *dz_out = nullptr) {
+  if (X != X) return kNone;  // 1. no reference sample
   const double *M = V.M;
   const double xc = ((M[0] * X + M[1] * Y) + M[2] * Z) + M[3];  // 2.
   const double yc = ((M[4] * X + M[5] * Y) + M[6] * Z) + M[7];
   const double zc = ((M[8] * X + M[9] * Y) + M[10] * Z) + M[11];
-  if (!(zc > 0)) return;
+  if (!(zc > 0)) return kNotInView;
   const double u = (V.fx * xc) / zc + V.cx;  // 3.
   const double v = (V.fy * yc) / zc + V.cy;
   const double c = __builtin_floor(u + 0.5), r = __builtin_floor(v + 0.5);
-  if (!(c >= 0 && c <= (double)(V.cols - 1) && r >= 0 && r <= (double)(V.rows - 1))) return;  // (NaN and the infinities fail)
-  a->n_inframe++;
+  if (!(c >= 0 && c <= (double)(V.cols - 1) && r >= 0 && r <= (double)(V.rows - 1))) return kNotInView;  // (NaN and the infinities fail)
   const int ci = (int)c, ri = (int)r;  // (in range: decided above)
   const double zt = (double)V.d1[(size_t)ri * (size_t)V.cols + (size_t)ci] * V.factor;  // 4.
-  if (zt < 0.01 || zt > 100) return;
-  a->n_both++;
+  if (zt < 0.01 || zt > 100) return kNoTargetDepth;
   const double tol = V.tol_abs + V.tol_rel * zt;  // 5.
   const double dz = zc - zt;
-  if (dz > tol) { a->n_occluded++; return; }
-  if (dz < -tol) { a->n_through++; return; }
+  if (dz_out) *dz_out = dz;
+  if (dz > tol) return kOccluded;
+  if (dz < -tol) return kThrough;
+  return kConsistent;
+}
+
+// One reference sample into the running counts `a`: the class, counted.
+NID_DC_HD void sample(const View &V, double X, double Y, double Z, nid_depth_cell *a) {
+  double dz = 0;
+  const Class k = classify(V, X, Y, Z, &dz);
+  if (k == kNone) return;
+  a->n_ref++;
+  if (k == kNotInView) return;
+  a->n_inframe++;
+  if (k == kNoTargetDepth) return;
+  a->n_both++;
+  if (k == kOccluded) { a->n_occluded++; return; }
+  if (k == kThrough) { a->n_through++; return; }
   a->n_consistent++;
   const double um = (dz < 0 ? -dz : dz) * 1e6 + 0.5;
   a->sum_abs_um += um < kUmSaturated ? (uint64_t)um : (uint64_t)1 << 63;  // (um >= 0.5, or NaN -- a NaN factor --: the second arm)
@@ -100,6 +127,94 @@ NID_DC_HD bool promote(const nid_track_policy &P, const nid_depth_counts &chosen
   if (P.keyframe_mode == 0) return true;
   if ((double)chosen.n_inframe < P.min_overlap * (double)chosen.n_ref) return true;
   return P.max_age > 0 && age >= P.max_age;
+}
+
+
+// ---- nid_refmask.h --------------------------------------------------------------------------------------------------------
+// The set-up's back-projection of one pixel (k_tile calls it: ITS operations in its order): z in metres, the validity
+// test, x0, y0, the three rows of the column-major T_wc.  false -- and X, Y, Z untouched -- where the depth is not valid.
+NID_DC_HD bool backproject(double z, int r, int col, double fx, double fy, double cx, double cy, const double *Twc, double *X,
+                           double *Y, double *Z) {
+  if (z < 0.01 || z > 100) return false;  // CudaPoints3d.cu:12
+  const double x0 = z * (col - cx) / fx;
+  const double y0 = z * (r - cy) / fy;
+  *X = Twc[0] * x0 + Twc[4] * y0 + Twc[8] * z + Twc[12];
+  *Y = Twc[1] * x0 + Twc[5] * y0 + Twc[9] * z + Twc[13];
+  *Z = Twc[2] * x0 + Twc[6] * y0 + Twc[10] * z + Twc[14];
+  return true;
+}
+
+// what one masking call's pixels share besides the View of the target
+struct Keyframe {
+  const uint16_t *d0;  // the pristine depth, rows x cols
+  double factor;
+  const double *Twc;  // column-major 16
+};
+
+// Steps 1 - 3 of nid_refmask.h for pixel (r, col): the byte behind the classification, from the byte before it.
+NID_DC_HD uint8_t mask_classified(const View &V, const Keyframe &K, int r, int col, uint8_t old, int classes, int accumulate) {
+  uint8_t b = (uint8_t)(old & (accumulate ? 15 : NID_REFMASK_CALLER));
+  double X, Y, Z;
+  if (!backproject((double)K.d0[(size_t)r * (size_t)V.cols + (size_t)col] * K.factor, r, col, V.fx, V.fy, V.cx, V.cy, K.Twc, &X, &Y, &Z)) return b;
+  const Class k = classify(V, X, Y, Z);
+  if (k == kOccluded && (classes & NID_REFMASK_OCCLUDED)) b |= NID_REFMASK_OCCLUDED;
+  if (k == kThrough && (classes & NID_REFMASK_THROUGH)) b |= NID_REFMASK_THROUGH;
+  return b;
+}
+
+constexpr int kClassBits = NID_REFMASK_OCCLUDED | NID_REFMASK_THROUGH;
+
+// Step 4 for one pixel: the final byte from the classified byte and whether a pixel of S lies in its window.
+NID_DC_HD uint8_t mask_final(uint8_t classified, bool near_S) {
+  if (classified & kClassBits) return (uint8_t)(classified & ~NID_REFMASK_DILATED);
+  return near_S ? (uint8_t)(classified | NID_REFMASK_DILATED) : classified;
+}
+
+// one pixel of the final plane into the counts
+NID_DC_HD void mask_count(uint8_t b, bool valid, nid_refmask_counts *n) {
+  n->n_valid += valid;
+  n->n_caller += (b & NID_REFMASK_CALLER) != 0;
+  n->n_occluded += (b & NID_REFMASK_OCCLUDED) != 0;
+  n->n_through += (b & NID_REFMASK_THROUGH) != 0;
+  n->n_dilated += (b & NID_REFMASK_DILATED) != 0;
+  n->n_masked += valid && b;
+}
+
+NID_DC_HD bool depth_valid(uint16_t d, double factor) {
+  const double z = (double)d * factor;
+  return !(z < 0.01 || z > 100);
+}
+
+// nid_refmask_host behind its argument checks: THE RULE over the whole plane, in place.  The window of step 4 is searched
+// pixel by pixel (the device's dilation is separable: two ways to the same set).
+inline void refmask_host(const View &V, const Keyframe &K, int classes, int dilate, int accumulate, uint8_t *mask, nid_refmask_counts *counts) {
+  const int rows = V.rows, cols = V.cols;
+  for (int r = 0; r < rows; r++)
+    for (int c = 0; c < cols; c++) {
+      uint8_t &b = mask[(size_t)r * (size_t)cols + (size_t)c];
+      b = mask_classified(V, K, r, c, b, classes, accumulate);
+    }
+  // (step 4 changes bit 8 alone, S is read from bits 2 and 4: the plane can be finished in place)
+  nid_refmask_counts n = {};
+  for (int r = 0; r < rows; r++)
+    for (int c = 0; c < cols; c++) {
+      const size_t i = (size_t)r * (size_t)cols + (size_t)c;
+      bool near_S = false;
+      if (dilate > 0 && !(mask[i] & kClassBits)) {
+        const int r0 = r - dilate < 0 ? 0 : r - dilate, r1 = r + dilate > rows - 1 ? rows - 1 : r + dilate;
+        const int c0 = c - dilate < 0 ? 0 : c - dilate, c1 = c + dilate > cols - 1 ? cols - 1 : c + dilate;
+        for (int rr = r0; rr <= r1 && !near_S; rr++)
+          for (int cc = c0; cc <= c1; cc++)
+            if (mask[(size_t)rr * (size_t)cols + (size_t)cc] & kClassBits) { near_S = true; break; }
+      }
+      mask[i] = mask_final(mask[i], near_S);
+      mask_count(mask[i], depth_valid(K.d0[i], K.factor), &n);
+    }
+  if (counts) *counts = n;
+}
+
+NID_DC_HD bool refmask_args_ok(double tol_abs, double tol_rel, int classes, int dilate) {
+  return finite_nonneg(tol_abs) && finite_nonneg(tol_rel) && (classes & ~kClassBits) == 0 && dilate >= 0 && dilate <= NID_REFMASK_MAX_DILATE;
 }
 
 }  // namespace dc

@@ -26,6 +26,20 @@ struct nid_pyr {
     PinnedBuf<unsigned long long> stage;     // the matrices (as doubles), then the totals
     PinnedBuf<nid_depth_cell> cells_host;    // grown to what a call with cells != NULL asks for
   } dc;
+  // nid_refmask.inc: the reference's depth factor (remembered by whatever makes a reference), and the mask's state and
+  // buffers -- made by the first masking call behind a new reference (have_pristine), never by a caller who does not mask
+  struct RefMask {
+    double ref_factor = 0;
+    bool have_pristine = false;  // pristine_dev / mask_dev belong to the resident reference
+    bool any_masked = false;     // a byte of mask_dev is non-zero
+    DevBuf<uint16_t> pristine_dev;           // level 0's reference depth as it was made
+    DevBuf<uint8_t> mask_dev, work_dev;      // the plane; the classified bytes of the call under way
+    DevBuf<unsigned long long> counts_dev;   // [8]
+    PinnedBuf<unsigned long long> counts_host;
+    PinnedBuf<uint8_t> plane_host;           // nid_pyr_set_reference_mask_u8's plane on its way up
+    // a new reference starts unmasked
+    void new_reference(double factor) { ref_factor = factor; have_pristine = any_masked = false; }
+  } rm;
 };
 
 namespace {
@@ -145,6 +159,7 @@ int nid_pyr_set_pair_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_fac
   if (rc) return rc;
   // from here on the levels are being overwritten: none of them is ready until the stream has drained
   p->have_pair = p->have_tdepth = false;
+  p->rm.new_reference(depth_factor);  // (nid_refmask.h: no mask, no pristine copy)
   for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_target = p->ctx[l]->have_href = false;
   if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];

@@ -25,12 +25,16 @@ struct nid_track {
   nid_track_policy policy = {0, 0, 0, 0, 0.0, 0.0, 0.01, 0.02};
   int32_t age = 0, n_checked = 0;
   nid_depth_counts chosen = {};
+  // nid_refmask.h (nid_refmask.inc): the classes masked behind a frame tracked on the keyframe (0: masking is off), the
+  // dilation, and the counts of the last push's step 5e
+  int32_t mask_classes = 0, mask_dilate = 0;
+  nid_refmask_counts last_mask = {}, push_mask = {};  // (push_mask: of the push under way, kept when it returns NID_OK)
 };
 
 namespace {
 
 // A later frame with depth under an active policy (nid_keyframe.inc, behind this file): steps 5a - 5d of nid_keyframe.h
-// on the chains nid_pyr_multistart_lm left in t->results / t->origin.  It moves cur / prev as nid_track_push_u16 does, behind
+// (and, with masking set, step 5e of nid_refmask.h) on the chains nid_pyr_multistart_lm left in t->results / t->origin.  It moves cur / prev as nid_track_push_u16 does, behind
 // its last call that can fail; the age and the last check's record are nid_track_push_u16's to keep.
 int track_finish_with_policy(nid_track *t, int n, nid_track_result *R, nid_depth_counts *chosen, int32_t *n_checked);
 
@@ -44,6 +48,7 @@ int pyr_promote(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, cons
   if (rc) return rc;
   // from here on the reference is being overwritten: no level has one until the stream has drained
   p->have_pair = false;
+  p->rm.new_reference(depth_factor);  // (nid_refmask.h: no mask, no pristine copy)
   for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_href = false;
   if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
@@ -202,6 +207,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   R.frame = t->frame;
   nid_depth_counts chosen = {};  // (nid_keyframe.h: what this push checked, kept with the poses when it returns NID_OK)
   int32_t n_checked = 0;
+  t->push_mask = nid_refmask_counts();  // (nid_refmask.h: step 5e's counts, if this push runs it)
   int rc = nid_pyr_set_target_u8(p, im);
   if (rc) return rc;
   if (first) {
@@ -264,6 +270,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   else if (R.status == NID_TRACK_OK) t->age++;
   t->chosen = chosen;
   t->n_checked = n_checked;
+  t->last_mask = t->push_mask;
   t->frame++;
   *out = R;
   return NID_OK;

@@ -1,7 +1,8 @@
 // nid_setup_kernels.hip.h -- the once-per-pair kernels: back-projection + tiling, the target image's margins, the reference
 // stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
 // next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth), the depth-consistency check of the
-// keyframe's points against the target's depth (k_depth_check).
+// keyframe's points against the target's depth (k_depth_check), the reference mask (k_refmask_classify,
+// k_refmask_dilate_apply).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
@@ -35,15 +36,7 @@ __global__ void k_tile(Geometry g, const double *__restrict__ depth,
     i0 = im0[id];
     bool valid;
     if (depth) {
-      const double z = depth[id];
-      valid = !(z < 0.01 || z > 100);  // CudaPoints3d.cu:12
-      if (valid) {
-        const double x0 = z * (col - g.cx) / g.fx;
-        const double y0 = z * (r - g.cy) / g.fy;
-        X = Twc[0] * x0 + Twc[4] * y0 + Twc[8] * z + Twc[12];
-        Y = Twc[1] * x0 + Twc[5] * y0 + Twc[9] * z + Twc[13];
-        Z = Twc[2] * x0 + Twc[6] * y0 + Twc[10] * z + Twc[14];
-      }
+      valid = dc::backproject(depth[id], r, col, g.fx, g.fy, g.cx, g.cy, Twc, &X, &Y, &Z);  // (shared with nid_refmask.h's rule)
       if (points_out) {
         points_out[3 * id] = X; points_out[3 * id + 1] = Y; points_out[3 * id + 2] = Z;
       }
@@ -256,6 +249,103 @@ __global__ void __launch_bounds__(256) k_depth_check(Geometry g, Tiles t, DepthC
     else out->sum_abs_um = s;
     atomicAdd(A.totals + (size_t)pose * 8 + tid, s);
   }
+}
+
+// The reference mask (nid/nid_refmask.h), two kernels behind each other on one stream.
+//
+// k_refmask_classify: image order, one lane per pixel of level 0 -- the pristine u16 depth and the u8 plane are read and
+// the classified byte is written at the lane's own index (coalesced); the one gather is the target depth where the
+// pixel's point projects.  Each lane runs dc::mask_classified (nid_depth_check.h: the host's text): the set-up's
+// back-projection of the PRISTINE depth, the check's class, the byte.  `work` is a plane of its own: the next kernel reads
+// neighbours' bytes of it while it writes the final plane.
+struct RefMaskArgs {
+  double M[12];         // rows of [R|t] of the pose (lm::pose_record)
+  const uint16_t *d0;   // the keyframe's pristine depth, rows x cols
+  const double *Twc;    // its camera -> world matrix, column-major 16
+  const uint16_t *d1;   // the target's depth, rows x cols
+  double factor0, factor1, tol_abs, tol_rel;
+  int classes, accumulate;
+};
+static_assert(sizeof(nid_refmask_counts) == 64, "nid_refmask.h's record");
+
+__global__ void __launch_bounds__(256) k_refmask_classify(Geometry g, RefMaskArgs A, const uint8_t *__restrict__ mask, uint8_t *__restrict__ work) {
+  const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (long)g.rows * g.cols) return;
+  dc::View V;
+#pragma unroll
+  for (int k = 0; k < 12; k++) V.M[k] = A.M[k];
+  V.fx = g.fx; V.fy = g.fy; V.cx = g.cx; V.cy = g.cy;
+  V.rows = g.rows; V.cols = g.cols;
+  V.d1 = A.d1; V.factor = A.factor1; V.tol_abs = A.tol_abs; V.tol_rel = A.tol_rel;
+  const dc::Keyframe K = {A.d0, A.factor0, A.Twc};
+  work[id] = dc::mask_classified(V, K, (int)(id / g.cols), (int)(id % g.cols), mask[id], A.classes, A.accumulate);
+}
+
+// k_refmask_dilate_apply: ONE workgroup per kRmTileH x kRmTileW image tile (a wave is one tile row: its byte and u16
+// accesses are 64 adjacent elements).  The flags "the classified byte carries bit 2 or 4" of the tile and its halo of
+// NID_REFMASK_MAX_DILATE -- zero outside the image, which clips the window -- go to LDS; the dilation is separable: rows
+// (every tile row and halo row), then columns.  Each lane then makes four pixels: the final byte (dc::mask_final), the
+// masked depth pristine-or-0 of level 0 in the same pass, and the pixel's counts (dc::mask_count).  The counts -- six of
+// nid_refmask_counts and the non-zero bytes -- are summed over the wave with shuffles, over the four waves in LDS, and
+// lanes 0 .. 6 add them to the call's totals with ONE 64-bit INTEGER atomic each (exact, order-independent).
+constexpr int kRmTileW = 64, kRmTileH = 16, kRmHalo = NID_REFMASK_MAX_DILATE;
+constexpr int kRmCountWords = 7;  // n_valid, n_caller, n_occluded, n_through, n_dilated, n_masked, non-zero bytes
+static_assert(kRmTileW * 4 == 256 && kRmTileH % 4 == 0, "256 lanes: a wave per tile row, four passes");
+
+__global__ void __launch_bounds__(256) k_refmask_dilate_apply(int rows, int cols, int dilate, const uint8_t *__restrict__ work,
+                                                              const uint16_t *__restrict__ pristine, double factor,
+                                                              uint8_t *__restrict__ mask, uint16_t *__restrict__ depth,
+                                                              unsigned long long *__restrict__ totals /*[8], zero before the launch*/) {
+  constexpr int SW = kRmTileW + 2 * kRmHalo, SH = kRmTileH + 2 * kRmHalo;
+  __shared__ uint8_t src[SH][SW];
+  __shared__ uint8_t rowd[SH][kRmTileW];
+  __shared__ unsigned long long part[4][8];
+  const int tid = threadIdx.x;
+  const int r0 = (int)blockIdx.y * kRmTileH, c0 = (int)blockIdx.x * kRmTileW;
+  const int d = dilate < 0 ? 0 : (dilate > kRmHalo ? kRmHalo : dilate);
+  for (int e = tid; e < SH * SW; e += 256) {
+    const int lr = e / SW, lc = e % SW;
+    const int r = r0 - kRmHalo + lr, c = c0 - kRmHalo + lc;
+    uint8_t f = 0;
+    if (r >= 0 && r < rows && c >= 0 && c < cols) f = (work[(size_t)r * cols + c] & dc::kClassBits) ? 1 : 0;
+    src[lr][lc] = f;
+  }
+  __syncthreads();
+  for (int e = tid; e < SH * kRmTileW; e += 256) {
+    const int lr = e / kRmTileW, lc = e % kRmTileW;
+    uint8_t f = 0;
+    for (int k = -d; k <= d; k++) f |= src[lr][lc + kRmHalo + k];
+    rowd[lr][lc] = f;
+  }
+  __syncthreads();
+  nid_refmask_counts n = {};
+  int nonzero = 0;
+  for (int e = tid; e < kRmTileH * kRmTileW; e += 256) {
+    const int lr = e / kRmTileW, lc = e % kRmTileW;
+    const int r = r0 + lr, c = c0 + lc;
+    if (r >= rows || c >= cols) continue;
+    uint8_t f = 0;
+    for (int k = -d; k <= d; k++) f |= rowd[lr + kRmHalo + k][lc];
+    const size_t i = (size_t)r * cols + c;
+    const uint8_t b = dc::mask_final(work[i], d > 0 && f);
+    const uint16_t z = pristine[i];
+    mask[i] = b;
+    depth[i] = b ? (uint16_t)0 : z;
+    dc::mask_count(b, dc::depth_valid(z, factor), &n);
+    nonzero += b != 0;
+  }
+  int cnt[kRmCountWords] = {(int)n.n_valid, (int)n.n_caller, (int)n.n_occluded, (int)n.n_through, (int)n.n_dilated, (int)n.n_masked, nonzero};
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < kRmCountWords; k++) cnt[k] += __shfl_down(cnt[k], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kRmCountWords; k++) part[tid >> 6][k] = (unsigned long long)cnt[k];
+  }
+  __syncthreads();
+  if (tid < kRmCountWords) atomicAdd(totals + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
 }
 
 // depth pixels that belong to no cell (rows/cols not divisible by cell_num, Q11)
