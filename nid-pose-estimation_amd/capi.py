@@ -123,6 +123,14 @@ REFMASK_COUNTS_DTYPE = np.dtype([("n_valid", "i8"), ("n_caller", "i8"), ("n_occl
                                  ("n_masked", "i8"), ("reserved", "i8", 2)])
 assert REFMASK_COUNTS_DTYPE.itemsize == 64
 
+# include/nid/nid_reffill.h (likewise: depth for the reference's holes from tracked frames, the tracker's use of it)
+REFFILL_SYMBOLS = ["nid_pyr_fill_reference_depth", "nid_pyr_clear_reference_fill", "nid_pyr_get_reference_fill_u16", "nid_reffill_host",
+                   "nid_track_set_filling", "nid_track_last_fill"]
+REFFILL_MAX_GUARD = 2
+REFFILL_COUNTS_DTYPE = np.dtype([("n_target_valid", "i8"), ("n_splat", "i8"), ("n_hit", "i8"), ("n_holes", "i8"), ("n_refused", "i8"),
+                                 ("n_new", "i8"), ("n_filled", "i8"), ("reserved", "i8")])
+assert REFFILL_COUNTS_DTYPE.itemsize == 64
+
 _lib = None
 
 
@@ -256,6 +264,15 @@ def load():
                                          C.c_int, C.c_int, C.c_int, c_u8p, vp]
         lib.nid_track_set_masking.argtypes = [vp, C.c_int, C.c_int]
         lib.nid_track_last_mask.argtypes = [vp, vp]
+    if hasattr(lib, "nid_pyr_fill_reference_depth"):   # (likewise)
+        u16p = C.POINTER(C.c_uint16)
+        lib.nid_pyr_fill_reference_depth.argtypes = [vp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        lib.nid_pyr_clear_reference_fill.argtypes = [vp]
+        lib.nid_pyr_get_reference_fill_u16.argtypes = [vp, u16p]
+        lib.nid_reffill_host.argtypes = [C.POINTER(NidConfig), u16p, C.c_double, c_dp, u16p, C.c_double, c_dp, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, u16p, vp]
+        lib.nid_track_set_filling.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.nid_track_last_fill.argtypes = [vp, vp]
     _lib = lib
     return lib
 
@@ -797,6 +814,24 @@ class Pyramid:
         self._check(self.lib.nid_pyr_get_reference_mask_u8(self.h, m.ctypes.data_as(c_u8p)), "nid_pyr_get_reference_mask_u8")
         return m
 
+    def fill_reference_depth(self, pose7, guard=1, guard_abs=50, guard_rel_1024=20, accumulate=False):
+        """nid_pyr_fill_reference_depth: the counts as a REFFILL_COUNTS_DTYPE record."""
+        q = _d(pose7)
+        assert q.size == 7
+        n = np.zeros(1, dtype=REFFILL_COUNTS_DTYPE)
+        self._check(self.lib.nid_pyr_fill_reference_depth(self.h, _dp(q), int(guard), int(guard_abs), int(guard_rel_1024), int(accumulate),
+                                                          n.ctypes.data_as(C.c_void_p)), "nid_pyr_fill_reference_depth")
+        return n[0]
+
+    def clear_reference_fill(self):
+        self._check(self.lib.nid_pyr_clear_reference_fill(self.h), "nid_pyr_clear_reference_fill")
+
+    def get_reference_fill(self):
+        """nid_pyr_get_reference_fill_u16: the plane (rows x cols of level 0) as the device holds it."""
+        f = np.zeros((self.cfg0.rows, self.cfg0.cols), dtype=np.uint16)
+        self._check(self.lib.nid_pyr_get_reference_fill_u16(self.h, f.ctypes.data_as(C.POINTER(C.c_uint16))), "nid_pyr_get_reference_fill_u16")
+        return f
+
     def get_level_inputs(self, level):
         """(depth_u16, im0, im1) of a level as the device holds them."""
         c = self.level_config(level)
@@ -953,6 +988,16 @@ class Tracker:
         self._check(self.lib.nid_track_last_mask(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_mask")
         return n[0]
 
+    def set_filling(self, on, guard=1, guard_abs=50, guard_rel_1024=20):
+        """nid_track_set_filling (nid_reffill.h): off by default"""
+        self._check(self.lib.nid_track_set_filling(self.h, int(on), int(guard), int(guard_abs), int(guard_rel_1024)), "nid_track_set_filling")
+
+    def last_fill(self):
+        """nid_track_last_fill: the counts of the last push's fill as a REFFILL_COUNTS_DTYPE record (zeros: it ran none)"""
+        n = np.zeros(1, dtype=REFFILL_COUNTS_DTYPE)
+        self._check(self.lib.nid_track_last_fill(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_fill")
+        return n[0]
+
     def push(self, im, depth_u16=None, depth_factor=1.0 / 5000, T_wc_first=None):
         """nid_track_push_u16: one frame.  Returns a dict of nid_track_result's members (pose7 and rounds as arrays)."""
         N = self.cfg0.rows * self.cfg0.cols
@@ -1015,6 +1060,28 @@ def refmask_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1,
     if rc != NID_OK:
         raise NidError(f"nid_refmask_host: {lib.nid_status_string(rc).decode()} ({rc})")
     return m.reshape(cfg.rows, cfg.cols), n[0]
+
+
+def reffill_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1, pose7, guard=1, guard_abs=50, guard_rel_1024=20,
+                 accumulate=False, fill=None):
+    """nid_reffill_host (nid_reffill.h): one call of the rule on a copy of `fill` (None: zeros): (plane [rows, cols] u16,
+    counts as a REFFILL_COUNTS_DTYPE record) -- what nid_pyr_fill_reference_depth computes, from the same text compiled for
+    the host."""
+    lib = load()
+    N = cfg.rows * cfg.cols
+    u16p = C.POINTER(C.c_uint16)
+    d0 = np.ascontiguousarray(depth0_u16, dtype=np.uint16).reshape(-1)
+    d1 = np.ascontiguousarray(depth1_u16, dtype=np.uint16).reshape(-1)
+    T, q = _d(T_wc_colmajor16), _d(pose7)
+    f = np.zeros(N, dtype=np.uint16) if fill is None else np.array(fill, dtype=np.uint16).reshape(-1)
+    assert d0.size == N and d1.size == N and f.size == N and T.size == 16 and q.size == 7
+    n = np.zeros(1, dtype=REFFILL_COUNTS_DTYPE)
+    rc = lib.nid_reffill_host(C.byref(cfg), d0.ctypes.data_as(u16p), float(factor0), _dp(T), d1.ctypes.data_as(u16p), float(factor1), _dp(q),
+                              int(guard), int(guard_abs), int(guard_rel_1024), int(accumulate), f.ctypes.data_as(u16p),
+                              n.ctypes.data_as(C.c_void_p))
+    if rc != NID_OK:
+        raise NidError(f"nid_reffill_host: {lib.nid_status_string(rc).decode()} ({rc})")
+    return f.reshape(cfg.rows, cfg.cols), n[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------

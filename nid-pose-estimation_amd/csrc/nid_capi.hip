@@ -2158,3 +2158,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- a per-pixel mask on the resident pyramid's reference and the tracker's use of it (include/nid/nid_refmask.h) ---
 #include "nid_refmask.inc"
+
+// ---- depth for the reference's holes from tracked frames and the tracker's use of it (include/nid/nid_reffill.h) -----
+#include "nid_reffill.inc"

@@ -63,8 +63,11 @@ int track_finish_with_policy(nid_track *t, int n, nid_track_result *R, nid_depth
     track::pose_to_Twc16(best.pose7, Twc);
     if ((rc = nid_pyr_promote_target(p, Twc))) return rc;
     R->promoted = 1;
-  } else if (t->mask_classes) {  // 5e. (nid_refmask.h): the keyframe stays, without what this frame no longer sees of it
-    if ((rc = nid_pyr_mask_occluded(p, best.pose7, P.tol_abs, P.tol_rel, t->mask_classes, t->mask_dilate, 0, &t->push_mask))) return rc;
+  } else {
+    // (nid_reffill.h): the keyframe stays, with this frame's depth where it has none; the first fill of a pixel stays
+    if (t->fill_on && (rc = nid_pyr_fill_reference_depth(p, best.pose7, t->fill_guard, t->fill_guard_abs, t->fill_guard_rel_1024, 1, &t->push_fill))) return rc;
+    // 5e. (nid_refmask.h): ... without what this frame no longer sees of it
+    if (t->mask_classes && (rc = nid_pyr_mask_occluded(p, best.pose7, P.tol_abs, P.tol_rel, t->mask_classes, t->mask_dilate, 0, &t->push_mask))) return rc;
   }
   R->best_origin = org[order[pick]];
   R->chi2 = best.chi2;

@@ -37,8 +37,18 @@ struct nid_pyr {
     DevBuf<unsigned long long> counts_dev;   // [8]
     PinnedBuf<unsigned long long> counts_host;
     PinnedBuf<uint8_t> plane_host;           // nid_pyr_set_reference_mask_u8's plane on its way up
-    // a new reference starts unmasked
-    void new_reference(double factor) { ref_factor = factor; have_pristine = any_masked = false; }
+    // nid_reffill.inc: the fill's state and buffers -- made by the first fill behind a new reference (have_uploaded), never
+    // by a caller who does not fill.  With have_uploaded, pristine_dev holds fill ? fill : uploaded
+    struct Fill {
+      bool have_uploaded = false;  // uploaded_dev / fill_dev belong to the resident reference
+      bool any_filled = false;     // an entry of fill_dev is non-zero
+      DevBuf<uint16_t> uploaded_dev, fill_dev;  // level 0's reference depth as it was made; the plane
+      DevBuf<uint32_t> zbuf_dev;                // the z-buffer of the call under way
+      DevBuf<unsigned long long> counts_dev;    // [8]: nid_reffill_counts
+      PinnedBuf<unsigned long long> counts_host;
+    } fill;
+    // a new reference starts unmasked and unfilled
+    void new_reference(double factor) { ref_factor = factor; have_pristine = any_masked = fill.have_uploaded = fill.any_filled = false; }
   } rm;
 };
 

@@ -29,6 +29,11 @@ struct nid_track {
   // dilation, and the counts of the last push's step 5e
   int32_t mask_classes = 0, mask_dilate = 0;
   nid_refmask_counts last_mask = {}, push_mask = {};  // (push_mask: of the push under way, kept when it returns NID_OK)
+  // nid_reffill.h (nid_reffill.inc): whether a frame tracked on the keyframe fills its depth holes, the guard, and the
+  // counts of the last push's fill
+  bool fill_on = false;
+  int32_t fill_guard = 0, fill_guard_abs = 0, fill_guard_rel_1024 = 0;
+  nid_reffill_counts last_fill = {}, push_fill = {};  // (push_fill: as push_mask)
 };
 
 namespace {
@@ -208,6 +213,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   nid_depth_counts chosen = {};  // (nid_keyframe.h: what this push checked, kept with the poses when it returns NID_OK)
   int32_t n_checked = 0;
   t->push_mask = nid_refmask_counts();  // (nid_refmask.h: step 5e's counts, if this push runs it)
+  t->push_fill = nid_reffill_counts();  // (nid_reffill.h: the fill's counts, likewise)
   int rc = nid_pyr_set_target_u8(p, im);
   if (rc) return rc;
   if (first) {
@@ -271,6 +277,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   t->chosen = chosen;
   t->n_checked = n_checked;
   t->last_mask = t->push_mask;
+  t->last_fill = t->push_fill;
   t->frame++;
   *out = R;
   return NID_OK;

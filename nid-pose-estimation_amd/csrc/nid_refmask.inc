@@ -8,10 +8,18 @@
 // REFERENCE half of a promotion from there on (k_pyr_down_depth per coarser level, pair_u16_device_ref per level:
 // nid_pyr_stream.inc) and the counts' way home.  They open and close like the frame operations and leave every level as a
 // promotion does.  No evaluation kernel is launched, no SlotArgs filled, no slot touched.
+// nid_reffill.inc (behind this file) runs the same chain with a fourth front -- the plane as it is -- and its own kernels
+// between the pristine copy and the front (RmBefore): there the pristine depth is what a fill makes of the uploaded one.
 
 namespace {
 
-enum class RmFront { kCallerPlane, kZeros, kClassify };
+enum class RmFront { kCallerPlane, kZeros, kClassify, kKeep };  // (kKeep: the plane as it is -- nid_reffill.inc's front)
+
+// what a call puts between the pristine copy and the front (nid_reffill.inc: the kernels that rewrite pristine_dev)
+struct RmBefore {
+  int (*enqueue)(nid_pyr *p, const void *arg, hipStream_t st, const char *what);  // NID_OK, or the error behind pyr_fail
+  const void *arg;
+};
 
 int rm_ensure(nid_pyr *p, bool plane_host) {
   nid_ctx *c0 = p->ctx[0];
@@ -33,7 +41,8 @@ int rm_refuse(nid_pyr *p, const char *what) {
 }
 
 // the chain; A: k_refmask_classify's arguments but the planes (kClassify only), caller: the plane of kCallerPlane
-int rm_run(nid_pyr *p, RmFront front, const RefMaskArgs *A, const uint8_t *caller, int dilate, nid_refmask_counts *out, const char *what) {
+int rm_run(nid_pyr *p, RmFront front, const RefMaskArgs *A, const uint8_t *caller, int dilate, nid_refmask_counts *out, const char *what,
+           const RmBefore *before = nullptr) {
   nid_ctx *c0 = p->ctx[0];
   nid_pyr::RefMask &R = p->rm;
   // from here on the reference is being overwritten: no level has one until the stream has drained
@@ -51,12 +60,15 @@ int rm_run(nid_pyr *p, RmFront front, const RefMaskArgs *A, const uint8_t *calle
     if (hipMemsetAsync(R.mask_dev, 0, N, st) != hipSuccess) return failed("hipMemsetAsync(mask)");
   }
   if (hipMemsetAsync(R.counts_dev, 0, 8 * sizeof(unsigned long long), st) != hipSuccess) return failed("hipMemsetAsync(counts)");
+  if (before && (rc = before->enqueue(p, before->arg, st, what))) return pyr_drain(p, rc);
   if (front == RmFront::kCallerPlane) {
     uint8_t *h = R.plane_host;
     for (size_t i = 0; i < N; i++) h[i] = caller[i] ? NID_REFMASK_CALLER : 0;
     if (hipMemcpyAsync(R.work_dev, h, N, hipMemcpyHostToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(mask)");
   } else if (front == RmFront::kZeros) {
     if (hipMemsetAsync(R.work_dev, 0, N, st) != hipSuccess) return failed("hipMemsetAsync(work)");
+  } else if (front == RmFront::kKeep) {  // (a final plane through dc::mask_final with dilate 0 is itself)
+    if (hipMemcpyAsync(R.work_dev, R.mask_dev, N, hipMemcpyDeviceToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(work)");
   } else {
     RefMaskArgs a = *A;
     a.d0 = R.pristine_dev; a.Twc = c0->Twc_dev; a.d1 = p->tdepth_dev;

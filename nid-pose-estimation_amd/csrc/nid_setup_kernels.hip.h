@@ -2,12 +2,13 @@
 // stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
 // next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth), the depth-consistency check of the
 // keyframe's points against the target's depth (k_depth_check), the reference mask (k_refmask_classify,
-// k_refmask_dilate_apply).
+// k_refmask_dilate_apply), the reference fill (k_reffill_splat, k_reffill_apply).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
 #include "nid_depth_check.h"
 #include "nid_kernels.hip.h"
+#include "nid_reffill_rule.h"
 
 namespace nid {
 
@@ -346,6 +347,119 @@ __global__ void __launch_bounds__(256) k_refmask_dilate_apply(int rows, int cols
   }
   __syncthreads();
   if (tid < kRmCountWords) atomicAdd(totals + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+}
+
+// The reference fill (nid/nid_reffill.h), two kernels behind each other on one stream, in front of the masking calls' chain.
+//
+// k_reffill_splat: image order, one lane per TARGET pixel of level 0 -- the u16 depth is read at the lane's own index
+// (coalesced); the one scatter is a 32-bit atomicMin into the keyframe's z-buffer (0xFF bytes before the launch) where
+// rf::splat (nid_reffill_rule.h: the host's text) sends the pixel.  n_target_valid and n_splat are summed over the wave with
+// shuffles, over the four waves in LDS, and lanes 0 and 1 add them to the call's totals with ONE 64-bit INTEGER atomic
+// each.  Every lane reaches the shuffles: a lane past the image counts nothing.
+struct RefFillArgs {
+  double M[12];        // rows of [R|t], target camera -> keyframe camera (rf::target_to_keyframe)
+  const uint16_t *d1;  // the target's depth, rows x cols
+  double factor1, factor0;
+};
+static_assert(sizeof(nid_reffill_counts) == 64 && offsetof(nid_reffill_counts, n_hit) == 16, "nid_reffill.h's record: the splat's two counts, then the apply's five");
+
+__global__ void __launch_bounds__(256) k_reffill_splat(Geometry g, RefFillArgs A, uint32_t *__restrict__ zbuf,
+                                                       unsigned long long *__restrict__ totals /*[8], zero before the launch*/) {
+  __shared__ unsigned long long part[4][2];
+  const int tid = threadIdx.x;
+  const long id = (long)blockIdx.x * blockDim.x + tid;
+  int cnt[2] = {0, 0};
+  if (id < (long)g.rows * g.cols) {
+    rf::Splat S;
+#pragma unroll
+    for (int k = 0; k < 12; k++) S.M[k] = A.M[k];
+    S.fx = g.fx; S.fy = g.fy; S.cx = g.cx; S.cy = g.cy;
+    S.rows = g.rows; S.cols = g.cols;
+    S.d1 = A.d1; S.factor1 = A.factor1; S.factor0 = A.factor0;
+    size_t idx = 0;
+    uint32_t q = 0;
+    const int k = rf::splat(S, (int)(id / g.cols), (int)(id % g.cols), &idx, &q);
+    cnt[0] = k >= 1;
+    cnt[1] = k == 2;
+    if (k == 2) atomicMin(zbuf + idx, q);  // (idx < rows cols: rf::splat's frame test)
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+    cnt[0] += __shfl_down(cnt[0], o, 64);
+    cnt[1] += __shfl_down(cnt[1], o, 64);
+  }
+  if ((tid & 63) == 0) {
+    part[tid >> 6][0] = (unsigned long long)cnt[0];
+    part[tid >> 6][1] = (unsigned long long)cnt[1];
+  }
+  __syncthreads();
+  if (tid < 2) atomicAdd(totals + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+}
+
+// k_reffill_apply: ONE workgroup per kRmTileH x kRmTileW image tile, a wave per tile row, as k_refmask_dilate_apply.  The
+// surface counts S(p) (rf::surface) of the tile and its halo of NID_REFFILL_MAX_GUARD -- none outside the image, which
+// clips the window -- go to LDS as 32-bit words.  Each lane then makes four pixels: the guard's window where the pixel's
+// fill hangs on it (rf::guard_decides, rf::behind), the fill (rf::apply) written over the plane's old value, the new
+// pristine depth fill-or-uploaded for the masking chain behind this kernel, and the pixel's five counts -- summed like the
+// mask's and added to words 2 .. 6 of the call's totals with ONE 64-bit INTEGER atomic each.
+constexpr int kRfHalo = NID_REFFILL_MAX_GUARD;
+constexpr int kRfCountWords = 5;  // n_hit, n_holes, n_refused, n_new, n_filled
+
+__global__ void __launch_bounds__(256) k_reffill_apply(int rows, int cols, int guard, int guard_abs, int guard_rel_1024, int accumulate,
+                                                       const uint32_t *__restrict__ zbuf, const uint16_t *__restrict__ uploaded, double factor0,
+                                                       uint16_t *__restrict__ fill, uint16_t *__restrict__ pristine,
+                                                       unsigned long long *__restrict__ totals /*[8]: words 2 .. 6*/) {
+  constexpr int SW = kRmTileW + 2 * kRfHalo, SH = kRmTileH + 2 * kRfHalo;
+  __shared__ uint32_t surf[SH][SW];
+  __shared__ unsigned long long part[4][8];
+  const int tid = threadIdx.x;
+  const int r0 = (int)blockIdx.y * kRmTileH, c0 = (int)blockIdx.x * kRmTileW;
+  const int d = guard < 0 ? 0 : (guard > kRfHalo ? kRfHalo : guard);
+  for (int e = tid; e < SH * SW; e += 256) {
+    const int lr = e / SW, lc = e % SW;
+    const int r = r0 - kRfHalo + lr, c = c0 - kRfHalo + lc;
+    uint32_t s = rf::kNone;
+    if (r >= 0 && r < rows && c >= 0 && c < cols) {
+      const size_t i = (size_t)r * cols + c;
+      s = rf::surface(zbuf[i], uploaded[i], factor0);
+    }
+    surf[lr][lc] = s;
+  }
+  __syncthreads();
+  nid_reffill_counts n = {};
+  for (int e = tid; e < kRmTileH * kRmTileW; e += 256) {
+    const int lr = e / kRmTileW, lc = e % kRmTileW;
+    const int r = r0 + lr, c = c0 + lc;
+    if (r >= rows || c >= cols) continue;
+    const size_t i = (size_t)r * cols + c;
+    const uint32_t z = zbuf[i];
+    const uint16_t up = uploaded[i], old = fill[i];
+    const bool valid = dc::depth_valid(up, factor0);
+    bool refused = false;
+    if (d > 0 && rf::guard_decides(valid, old, z != rf::kNone, accumulate)) {
+      for (int dr = -d; dr <= d; dr++)
+        for (int dc_ = -d; dc_ <= d; dc_++) {
+          if (dr == 0 && dc_ == 0) continue;
+          const uint32_t qn = surf[lr + kRfHalo + dr][lc + kRfHalo + dc_];
+          refused |= qn != rf::kNone && rf::behind(z, qn, guard_abs, guard_rel_1024);
+        }
+    }
+    const uint16_t f = rf::apply(valid, old, z, refused, accumulate, &n);
+    fill[i] = f;
+    pristine[i] = f ? f : up;
+  }
+  int cnt[kRfCountWords] = {(int)n.n_hit, (int)n.n_holes, (int)n.n_refused, (int)n.n_new, (int)n.n_filled};
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < kRfCountWords; k++) cnt[k] += __shfl_down(cnt[k], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < kRfCountWords; k++) part[tid >> 6][k] = (unsigned long long)cnt[k];
+  }
+  __syncthreads();
+  if (tid < kRfCountWords) atomicAdd(totals + 2 + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
 }
 
 // depth pixels that belong to no cell (rows/cols not divisible by cell_num, Q11)
