@@ -36,6 +36,17 @@ struct View {
   double factor, tol_abs, tol_rel;
 };
 
+// the View of one pose's matrix M, an image geometry g (Geometry on the device, nid_config on the host) and a call's arguments
+template <class G>
+NID_DC_HD View make_view(const G &g, const double *M, const uint16_t *d1, double factor, double tol_abs, double tol_rel) {
+  View V;
+  for (int k = 0; k < 12; k++) V.M[k] = M[k];
+  V.fx = g.fx; V.fy = g.fy; V.cx = g.cx; V.cy = g.cy;
+  V.rows = g.rows; V.cols = g.cols;
+  V.d1 = d1; V.factor = factor; V.tol_abs = tol_abs; V.tol_rel = tol_rel;
+  return V;
+}
+
 // The class of one reference sample (steps 1 - 5 of nid_keyframe.h), in the order the steps decide it
 enum Class : int {
   kNone = 0,           // 1. no reference sample

@@ -1,10 +1,10 @@
 // nid_keyframe.inc -- the depth-consistency check on the resident pyramid and the tracker's keyframe policy
 // (include/nid/nid_keyframe.h).  Part of nid_capi.hip's translation unit (included behind nid_pyr_stream.inc).
 //
-// The target's depth is a level-0 plane of the pyramid's own (nid_pyr::tdepth_dev).  nid_pyr_set_target_depth_u16 opens
-// and closes like the frame operations; nid_pyr_promote_target is nid_pyr_stream.inc's pyr_promote with the depth copied
-// on the device.  nid_pyr_depth_check runs k_depth_check (nid_setup_kernels.hip.h) on level 0's tiles, on level 0's
-// stream: the poses' matrices go up from the pyramid's pinned block in-stream -- one path for every n --, the per-pose
+// The target's depth is a level-0 plane of the pyramid's own (nid_pyr::tdepth_dev).  nid_pyr_set_target_depth_u16 stands
+// in nid_pyr.inc's frame over that part; nid_pyr_promote_target is nid_pyr_stream.inc's pyr_promote with the depth copied
+// on the device.  nid_pyr_depth_check rewrites nothing -- the frame over no part -- and runs k_depth_check
+// (nid_setup_kernels.hip.h) on level 0's tiles, on level 0's stream: the poses' matrices go up from the pyramid's pinned block in-stream -- one path for every n --, the per-pose
 // totals are 64-bit integer atomics behind the workgroups' reductions and come home through the same block, the cell
 // records only when asked for.  It launches no evaluation kernel, fills no SlotArgs and touches no slot.
 // The tracker's part is the back half of a frame under an active policy: one check, two decisions (nid_depth_check.h).
@@ -35,11 +35,7 @@ int track_finish_with_policy(nid_track *t, int n, nid_track_result *R, nid_depth
   const int32_t *org = t->origin.data() + (size_t)(L - 1) * n;
   // 5a. the candidates in rank order (the rule of nid_pyr_multistart_lm's survivors)
   std::vector<int> order;
-  for (int k = 0; k < n; k++)
-    if (row[k].n_active > 0 && std::isfinite(row[k].chi2)) order.push_back(k);
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    return row[a].chi2 / (double)row[a].n_active < row[b].chi2 / (double)row[b].n_active;
-  });
+  lm::rank_chains(row, n, order);
   // 5b. one check, over as many of them as the choice reads
   const int m = dc::candidates_to_check(P, (int)order.size());
   std::vector<double> poses(7 * (size_t)m);
@@ -89,10 +85,8 @@ int nid_pyr_set_target_depth_u16(nid_pyr *p, const uint16_t *depth_u16, double d
   if (!p || !depth_u16) return NID_ERR_INVALID_ARG;
   for (int l = 0; l < p->levels; l++)
     if (!p->ctx[l]->have_target) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_set_target_depth_u16: no target on level " + std::to_string(l));
-  int rc = pyr_refuse_pending(p, "nid_pyr_set_target_depth_u16");
+  int rc = pyr_open(p, "nid_pyr_set_target_depth_u16", kPyrTdepth);
   if (rc) return rc;
-  p->have_tdepth = false;  // being overwritten
-  if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
   if ((rc = pair_stage_ensure(c0))) return rc;  // (nothing enqueued yet)
   const PairStage L0 = pair_stage_layout(c0->g);
@@ -100,9 +94,8 @@ int nid_pyr_set_target_depth_u16(nid_pyr *p, const uint16_t *depth_u16, double d
   std::memcpy(c0->pair_stage + L0.depth, depth_u16, 2 * N);
   if (hipMemcpyAsync(p->tdepth_dev, c0->pair_stage + L0.depth, 2 * N, hipMemcpyHostToDevice, c0->stream) != hipSuccess)
     return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, "nid_pyr_set_target_depth_u16: hipMemcpyAsync(depth)"));
-  if ((rc = pyr_finish(p, "nid_pyr_set_target_depth_u16"))) return rc;
+  if ((rc = pyr_close(p, "nid_pyr_set_target_depth_u16", kPyrTdepth))) return rc;
   p->tdepth_factor = depth_factor;
-  p->have_tdepth = true;
   return NID_OK;
 }
 
@@ -117,9 +110,8 @@ int nid_pyr_depth_check(nid_pyr *p, const double *poses7, int n, double tol_abs,
   nid_ctx *c0 = p->ctx[0];
   if (!p->have_pair || !c0->have_ref) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_depth_check: no reference");
   if (!p->have_tdepth) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_depth_check: the target has no depth: nid_pyr_set_target_depth_u16() first");
-  int rc = pyr_refuse_pending(p, "nid_pyr_depth_check");
+  int rc = pyr_open(p, "nid_pyr_depth_check", 0);  // (it rewrites nothing: no part's flags go down)
   if (rc) return rc;
-  if ((rc = pyr_front(p))) return rc;
   const Geometry &g = c0->g;
   const size_t ncell = (size_t)g.nloc, nrec = (size_t)n * ncell;
   if ((rc = dc_ensure(p, cells ? nrec : 0))) return rc;
@@ -142,7 +134,7 @@ int nid_pyr_depth_check(nid_pyr *p, const double *poses7, int n, double tol_abs,
   if (hipGetLastError() != hipSuccess) return failed("the launch failed");
   if (hipMemcpyAsync(totals_host, D.totals_dev, (size_t)n * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess) return failed("hipMemcpyAsync(totals)");
   if (cells && hipMemcpyAsync(D.cells_host, D.cells_dev, nrec * sizeof(nid_depth_cell), hipMemcpyDeviceToHost, st) != hipSuccess) return failed("hipMemcpyAsync(cells)");
-  if ((rc = pyr_finish(p, "nid_pyr_depth_check"))) return rc;
+  if ((rc = pyr_close(p, "nid_pyr_depth_check", 0))) return rc;
   std::memcpy(totals, totals_host, (size_t)n * sizeof(nid_depth_counts));
   if (cells) {
     // the device's records are in the context's own cell order: cell cell_begin + cl * cell_stride (a pyramid owns all cells: cl itself)
@@ -157,13 +149,10 @@ int nid_depth_check_host(const nid_config *cfg, const double *points3d, const ui
   if (!cfg || !points3d || !depth1_u16 || !pose7 || (!total && !cells) || !dc_tolerances_ok(tol_abs, tol_rel)) return NID_ERR_INVALID_ARG;
   if (cfg->rows < 1 || cfg->cols < 1 || cfg->cell_num < 1 || cfg->cell_begin != 0 || cfg->cell_end != 0) return NID_ERR_INVALID_ARG;
   if ((int64_t)cfg->rows * cfg->cols > INT32_MAX) return NID_ERR_INVALID_ARG;
-  dc::View V;
-  double q7[7];
+  double q7[7], M[12];
   int32_t mode;
-  lm::pose_record(pose7, NID_XFORM_QUAT, q7, V.M, &mode);
-  V.fx = cfg->fx; V.fy = cfg->fy; V.cx = cfg->cx; V.cy = cfg->cy;
-  V.rows = cfg->rows; V.cols = cfg->cols;
-  V.d1 = depth1_u16; V.factor = depth_factor; V.tol_abs = tol_abs; V.tol_rel = tol_rel;
+  lm::pose_record(pose7, NID_XFORM_QUAT, q7, M, &mode);
+  const dc::View V = dc::make_view(*cfg, M, depth1_u16, depth_factor, tol_abs, tol_rel);
   const int cn = cfg->cell_num, rb = cfg->rows / cn, cb = cfg->cols / cn;  // k_tile's cell map
   nid_depth_counts sum = {};
   for (int ci = 0; ci < cn; ci++)

@@ -9,6 +9,9 @@
 
 #include <stdint.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "nid/nid_multistart.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -303,6 +306,18 @@ NID_LM_HD void lm_trace(const nid_ms_state *S, nid_ms_trace *T) {
   for (int i = 0; i < 7; i++) T->pose7[i] = S->pose7[i];
   T->flags = S->flags;
   T->status = S->status;
+}
+
+// THE RANK RULE of a batch of finished chains (host only): the eligible ones -- n_active > 0 and a finite chi2 -- by
+// chi2 / n_active ascending, the lower index winning ties.  order[0] is nid_multistart_lm's *best; nid_pyr_multistart_lm's
+// survivors and the tracker's candidates (nid_keyframe.h, step 5a) are its front.
+inline void rank_chains(const nid_ms_result *res, int m, std::vector<int> &order) {
+  order.clear();
+  for (int k = 0; k < m; k++)
+    if (res[k].n_active > 0 && finite(res[k].chi2)) order.push_back(k);
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    return res[a].chi2 / (double)res[a].n_active < res[b].chi2 / (double)res[b].n_active;
+  });
 }
 
 }  // namespace lm

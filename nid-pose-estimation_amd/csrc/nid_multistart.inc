@@ -168,7 +168,7 @@ int nid_multistart_lm(nid_ctx *ctx, const double *poses7_in, int n, int iteratio
     R.outer_iterations = S.outer_done;
     R.trials = S.trials_total;
     R.status = S.status;
-    if (S.started && S.n_active > 0 && lm::finite(S.chi2)) {
+    if (S.started && S.n_active > 0 && lm::finite(S.chi2)) {  // (the front of lm::rank_chains, found in passing)
       const double v = S.chi2 / (double)S.n_active;
       if (best_k < 0 || v < best_v) { best_k = k; best_v = v; }
     }

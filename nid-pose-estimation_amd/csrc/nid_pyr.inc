@@ -6,8 +6,10 @@
 // ONE stream, level 0's, in dependency order, and synchronises it once before it marks any level ready: a level's later
 // launches run on that level's own streams, and nothing of this call is in flight by then.  What a level's own streams may
 // still be running when the call begins (k_repair behind a collected launch) is put in front of it with one event per
-// stream, on the device.  nid_pyr_multistart_lm calls nid_compute_href and nid_multistart_lm as they are: it fills no
-// record and launches nothing of its own; the survivors of a level are a handful of comparisons on the host.
+// stream, on the device.  That opening and the close are the frame (pyr_open / pyr_close, below) in which every later call
+// that rewrites a level's inputs stands as well; the reference's way from level 0's depth plane down is pyr_ref_tail.
+// nid_pyr_multistart_lm calls nid_compute_href and nid_multistart_lm as they are: it fills no record and launches nothing
+// of its own; the survivors of a level are a handful of comparisons on the host (lm::rank_chains).
 
 struct nid_pyr {
   int levels = 0;
@@ -59,18 +61,41 @@ int pyr_fail(nid_pyr *p, int rc, const std::string &why) {
   return rc;
 }
 
-// The opening of every call that rewrites the levels' inputs (nid_pyr_set_pair_u16; nid_pyr_stream.inc's two), in two
-// steps with the caller's clearing of the ready flags between them.  REFUSE: NID_ERR_STATE while a level has an
-// uncollected launch.
+// THE FRAME of every call that rewrites the levels' inputs (nid_pyr_set_pair_u16; nid_pyr_stream.inc's, nid_keyframe.inc's
+// and nid_refmask.inc's): pyr_open, the call's own operations on level 0's stream in dependency order, pyr_close -- over
+// the PARTS the call owns.  A part's ready flags are down from pyr_open to a pyr_close that returned NID_OK.
+enum : unsigned { kPyrRef = 1, kPyrTarget = 2, kPyrTdepth = 4 };
+
+void pyr_mark(nid_pyr *p, unsigned parts, bool ready) {
+  for (int l = 0; l < p->levels; l++) {
+    nid_ctx *ctx = p->ctx[l];
+    if (parts & kPyrRef) {
+      ctx->have_ref = ready;
+      if (ready) ctx->ref_from_depth = true;  // (have_href stays false: the reference stage is the caller's)
+      else ctx->have_href = false;
+    }
+    if (parts & kPyrTarget) ctx->have_target = ready;
+  }
+  if (parts & kPyrRef) p->have_pair = ready;
+  if (parts & kPyrTdepth) p->have_tdepth = ready;
+}
+
+// REFUSE: NID_ERR_STATE, and nothing changed, while a level has an uncollected launch.
 int pyr_refuse_pending(nid_pyr *p, const char *what) {
   for (int l = 0; l < p->levels; l++)
     if (any_pending(p->ctx[l])) return pyr_fail(p, NID_ERR_STATE, std::string(what) + ": a launch is pending on level " + std::to_string(l) + ": nid_wait() it first");
   return NID_OK;
 }
 
-// FRONT: the device selected, resident evaluators retired, and what the levels' own streams still run -- it reads the
+// OPEN: the refusal; the parts' flags cleared -- from here on they are being overwritten -- and, where the call makes a NEW
+// reference (new_ref_factor: its depth factor) and not the resident one again, its mask and fill forgotten (nid_refmask.h);
+// then the device selected, resident evaluators retired, and what the levels' own streams still run -- it reads the
 // buffers the call rewrites -- put in front of level 0's stream, on the device, with one event per stream.
-int pyr_front(nid_pyr *p) {
+int pyr_open(nid_pyr *p, const char *what, unsigned parts, const double *new_ref_factor = nullptr) {
+  const int rc = pyr_refuse_pending(p, what);
+  if (rc) return rc;
+  pyr_mark(p, parts, false);
+  if (new_ref_factor) p->rm.new_reference(*new_ref_factor);
   nid_ctx *c0 = p->ctx[0];
   NID_HIP(c0, hipSetDevice(c0->cfg.device));
   for (int l = 0; l < p->levels; l++) resident_retire(p->ctx[l]);
@@ -87,24 +112,35 @@ int pyr_front(nid_pyr *p) {
   return NID_OK;
 }
 
-// The close: hipGetLastError behind the last launch, ONE synchronisation; an error drains the stream (nothing of the call
-// stays in flight).  The caller marks the levels ready after NID_OK.
+// an error behind pyr_open drains the stream: nothing of the call stays in flight
 int pyr_drain(nid_pyr *p, int rc) {
   (void)hipStreamSynchronize(p->ctx[0]->stream);
   return rc;
 }
 
-int pyr_finish(nid_pyr *p, const char *what) {
+// CLOSE: hipGetLastError behind the last launch, ONE synchronisation, and only then the parts' flags set.
+int pyr_close(nid_pyr *p, const char *what, unsigned parts) {
   nid_ctx *c0 = p->ctx[0];
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, std::string(what) + ": a launch failed: " + hipGetErrorString(e)));
   NID_HIP(c0, hipStreamSynchronize(c0->stream));
+  pyr_mark(p, parts, true);
   return NID_OK;
 }
 
 unsigned pyr_down_blocks(const nid_ctx *dst) {
   const long threads = (long)dst->g.rows * ((dst->g.cols + kPyrRun - 1) / kPyrRun);
   return (unsigned)((threads + 255) / 256);
+}
+
+// THE REFERENCE TAIL behind level 0's depth plane: the coarser levels' depth, then every level's points and tiles.
+void pyr_ref_tail(nid_pyr *p, double factor, hipStream_t st) {
+  for (int l = 1; l < p->levels; l++) {
+    nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
+    hipLaunchKernelGGL(k_pyr_down_depth, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->depth16_dev, factor,
+                       dst->depth16_dev);
+  }
+  for (int l = 0; l < p->levels; l++) pair_u16_device_ref(p->ctx[l], factor, st);
 }
 
 }  // namespace
@@ -165,13 +201,9 @@ nid_ctx *nid_pyr_level(nid_pyr *p, int level) { return (p && level >= 0 && level
 int nid_pyr_set_pair_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, const uint8_t *im0, const uint8_t *im1,
                          const double *Twc) {
   if (!p || !depth_u16 || !im0 || !im1 || !Twc) return NID_ERR_INVALID_ARG;
-  int rc = pyr_refuse_pending(p, "nid_pyr_set_pair_u16");
+  // (a pair's target comes without a depth of its own: that flag stays down)
+  int rc = pyr_open(p, "nid_pyr_set_pair_u16", kPyrRef | kPyrTarget | kPyrTdepth, &depth_factor);
   if (rc) return rc;
-  // from here on the levels are being overwritten: none of them is ready until the stream has drained
-  p->have_pair = p->have_tdepth = false;
-  p->rm.new_reference(depth_factor);  // (nid_refmask.h: no mask, no pristine copy)
-  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_target = p->ctx[l]->have_href = false;
-  if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
   const hipStream_t st = c0->stream;
   if ((rc = pair_u16_upload(c0, depth_u16, im0, im1, Twc, st))) return pyr_drain(p, rc);
@@ -184,14 +216,7 @@ int nid_pyr_set_pair_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_fac
                        src->depth16_dev, depth_factor, dst->im0_dev, dst->im1_dev, dst->depth16_dev);
   }
   for (int l = 0; l < p->levels; l++) pair_u16_device(p->ctx[l], depth_factor, st);
-  if ((rc = pyr_finish(p, "nid_pyr_set_pair_u16"))) return rc;
-  for (int l = 0; l < p->levels; l++) {
-    nid_ctx *ctx = p->ctx[l];
-    ctx->have_ref = ctx->have_target = true;  // (have_href stays false: the reference stage is the caller's)
-    ctx->ref_from_depth = true;
-  }
-  p->have_pair = true;
-  return NID_OK;
+  return pyr_close(p, "nid_pyr_set_pair_u16", kPyrRef | kPyrTarget);
 }
 
 int nid_pyr_get_level_inputs(nid_pyr *p, int level, uint16_t *depth_u16, uint8_t *im0, uint8_t *im1) {
@@ -219,8 +244,7 @@ int nid_pyr_multistart_lm(nid_pyr *p, const double *poses7_in, int n, const doub
   for (int l = 0; l + 1 < L; l++)
     if (kp[l] < 1 || kp[l] > kp[l + 1]) return pyr_fail(p, NID_ERR_INVALID_ARG, "nid_pyr_multistart_lm: 1 <= keep[l] <= keep[l+1]");
   if (!p->have_pair) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_multistart_lm: no pair set");
-  for (int l = 0; l < L; l++)
-    if (any_pending(p->ctx[l])) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_multistart_lm: a launch is pending on level " + std::to_string(l) + ": nid_wait() it first");
+  if (int rc = pyr_refuse_pending(p, "nid_pyr_multistart_lm")) return rc;
   std::memset(results, 0, (size_t)L * n * sizeof(nid_ms_result));
   std::fill(origin, origin + (size_t)L * n, (int32_t)-1);
   if (rounds) std::fill(rounds, rounds + L, (int32_t)0);
@@ -241,13 +265,7 @@ int nid_pyr_multistart_lm(nid_pyr *p, const double *poses7_in, int n, const doub
     if ((rc = nid_multistart_lm(ctx, cur.data(), m, iterations, delta, 0, res, nullptr, nullptr, &r))) return failed(rc);
     if (rounds) rounds[L - 1 - l] = r;
     std::copy(cur_origin.begin(), cur_origin.begin() + m, origin + (size_t)(L - 1 - l) * n);
-    // the eligible chains by chi2 / n_active ascending, the lower index winning ties (the rule of nid_multistart_lm's *best)
-    order.clear();
-    for (int k = 0; k < m; k++)
-      if (res[k].n_active > 0 && std::isfinite(res[k].chi2)) order.push_back(k);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-      return res[a].chi2 / (double)res[a].n_active < res[b].chi2 / (double)res[b].n_active;
-    });
+    lm::rank_chains(res, m, order);
     if (order.empty()) return NID_OK;  // (*best_origin is -1, the finer levels' rows are zero)
     if (l == 0) {
       if (best_origin) *best_origin = cur_origin[order[0]];

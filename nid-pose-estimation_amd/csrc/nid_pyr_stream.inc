@@ -2,11 +2,10 @@
 // resident target promoted to the reference, the pose helpers' C entry points and the tracker.
 // Part of nid_capi.hip's translation unit (included behind nid_pyr.inc): it works on the pyramid's and the levels' internals.
 //
-// The two frame operations open and close like nid_pyr_set_pair_u16 (pyr_refuse_pending, the ready flags of what is being
-// overwritten cleared, pyr_front, everything on level 0's stream in dependency order, pyr_finish, the flags set) and
-// enqueue the halves of its chain: the TARGET half (upload, k_pyr_down_u8 per coarser level, pair_u16_device_target per
-// level) or the REFERENCE half (im1 -> im0 on the device, depth upload, k_pyr_down_depth per coarser level, T_wc,
-// pair_u16_device_ref per level).  The tracker is a composition of these calls and nid_pyr_multistart_lm: it fills no pose
+// The two frame operations stand in nid_pyr.inc's frame (pyr_open over the part being overwritten, everything on level 0's
+// stream in dependency order, pyr_close) and enqueue the halves of nid_pyr_set_pair_u16's chain: the TARGET half (upload,
+// k_pyr_down_u8 per coarser level, pair_u16_device_target per level) or the REFERENCE half (im1 -> im0 on the device, depth
+// upload, T_wc, pyr_ref_tail).  The tracker is a composition of these calls and nid_pyr_multistart_lm: it fills no pose
 // record and launches no evaluation.
 
 struct nid_track {
@@ -49,13 +48,8 @@ int pyr_promote(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, cons
   for (int l = 0; l < p->levels; l++)
     if (!p->ctx[l]->have_target) return pyr_fail(p, NID_ERR_STATE, std::string(what) + ": no target on level " + std::to_string(l));
   if (!depth_u16 && !p->have_tdepth) return pyr_fail(p, NID_ERR_STATE, std::string(what) + ": the target has no depth: nid_pyr_set_target_depth_u16() first");
-  int rc = pyr_refuse_pending(p, what);
+  int rc = pyr_open(p, what, kPyrRef, &depth_factor);
   if (rc) return rc;
-  // from here on the reference is being overwritten: no level has one until the stream has drained
-  p->have_pair = false;
-  p->rm.new_reference(depth_factor);  // (nid_refmask.h: no mask, no pristine copy)
-  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_href = false;
-  if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
   const hipStream_t st = c0->stream;
   if ((rc = pair_stage_ensure(c0))) return rc;  // (nothing enqueued yet)
@@ -72,20 +66,8 @@ int pyr_promote(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, cons
          copy(ctx->Twc_dev, c0->pair_stage + L0.twc, 16 * sizeof(double), hipMemcpyHostToDevice);
   }
   if (!ok) return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, std::string(what) + ": hipMemcpyAsync"));
-  for (int l = 1; l < p->levels; l++) {
-    nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
-    hipLaunchKernelGGL(k_pyr_down_depth, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->depth16_dev, depth_factor,
-                       dst->depth16_dev);
-  }
-  for (int l = 0; l < p->levels; l++) pair_u16_device_ref(p->ctx[l], depth_factor, st);
-  if ((rc = pyr_finish(p, what))) return rc;
-  for (int l = 0; l < p->levels; l++) {
-    nid_ctx *ctx = p->ctx[l];
-    ctx->have_ref = true;  // (have_href stays false: the reference stage is the caller's)
-    ctx->ref_from_depth = true;
-  }
-  p->have_pair = true;
-  return NID_OK;
+  pyr_ref_tail(p, depth_factor, st);
+  return pyr_close(p, what, kPyrRef);
 }
 
 }  // namespace
@@ -94,12 +76,8 @@ extern "C" {
 
 int nid_pyr_set_target_u8(nid_pyr *p, const uint8_t *im1) {
   if (!p || !im1) return NID_ERR_INVALID_ARG;
-  int rc = pyr_refuse_pending(p, "nid_pyr_set_target_u8");
+  int rc = pyr_open(p, "nid_pyr_set_target_u8", kPyrTarget | kPyrTdepth);  // (nid_keyframe.h: a target's depth belongs to its image)
   if (rc) return rc;
-  // from here on the target is being overwritten: no level has one until the stream has drained
-  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_target = false;
-  p->have_tdepth = false;  // (nid_keyframe.h: a target's depth belongs to its image)
-  if ((rc = pyr_front(p))) return rc;
   nid_ctx *c0 = p->ctx[0];
   const hipStream_t st = c0->stream;
   if ((rc = pair_stage_ensure(c0))) return rc;  // (nothing enqueued yet)
@@ -113,9 +91,7 @@ int nid_pyr_set_target_u8(nid_pyr *p, const uint8_t *im1) {
     hipLaunchKernelGGL(k_pyr_down_u8, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->im1_dev, dst->im1_dev);
   }
   for (int l = 0; l < p->levels; l++) pair_u16_device_target(p->ctx[l], st);
-  if ((rc = pyr_finish(p, "nid_pyr_set_target_u8"))) return rc;
-  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_target = true;
-  return NID_OK;
+  return pyr_close(p, "nid_pyr_set_target_u8", kPyrTarget);
 }
 
 int nid_pyr_promote_target_u16(nid_pyr *p, const uint16_t *depth_u16, double depth_factor, const double *Twc) {

@@ -1,21 +1,16 @@
 // nid_reffill.inc -- depth for the holes of the resident pyramid's reference from tracked frames, and the tracker's use of
 // it (include/nid/nid_reffill.h).  Part of nid_capi.hip's translation unit (included behind nid_refmask.inc).
 //
-// A fill call is a masking call (nid_refmask.inc's rm_run) that keeps the plane and rewrites the PRISTINE depth in front
-// of it: behind the chain's own pristine copy come, on the same stream, the uploaded copy and a zero fill plane if this
-// is the first fill behind a new reference; then the z-buffer's 0xFF bytes, k_reffill_splat and k_reffill_apply (the fill
-// plane, pristine = fill ? fill : uploaded, the counts) -- or, for nid_pyr_clear_reference_fill, zeros into the plane and
-// the uploaded copy back into the pristine depth.  rm_run's back half (k_refmask_dilate_apply with the plane's own bytes
-// and dilate 0, k_pyr_down_depth per coarser level, pair_u16_device_ref per level) makes the effective reference of it
-// and closes the call with its one synchronisation.  No evaluation kernel is launched, no SlotArgs filled, no slot touched.
+// A fill call is a masking call (nid_refmask.inc's rm_begin ... rm_finish) that keeps the plane and rewrites the PRISTINE
+// depth in its middle.  rf_begin: behind rm_begin's own pristine copy come, on the same stream, the uploaded copy and a
+// zero fill plane if this is the first fill behind a new reference, and the fill's counts zeroed.  The call's own part:
+// the z-buffer's 0xFF bytes, k_reffill_splat and k_reffill_apply (the fill plane, pristine = fill ? fill : uploaded, the
+// counts) -- or, for nid_pyr_clear_reference_fill, zeros into the plane and the uploaded copy back into the pristine depth.
+// rf_finish: the counts' way home, the mask plane as it is into work_dev -- a final plane through dc::mask_final with
+// dilate 0 is itself --, and rm_finish, which makes the effective reference of it and closes the call with its one
+// synchronisation.  No evaluation kernel is launched, no SlotArgs filled, no slot touched.
 
 namespace {
-
-struct RfCall {
-  bool clear;  // nid_pyr_clear_reference_fill
-  RefFillArgs A;
-  int guard, guard_abs, guard_rel_1024, accumulate;
-};
 
 // the fill's buffers, made before anything of the call changes the pyramid
 int rf_ensure(nid_pyr *p) {
@@ -31,43 +26,40 @@ int rf_ensure(nid_pyr *p) {
   return NID_OK;
 }
 
-// rm_run's RmBefore: pristine_dev is the reference's pristine depth by now, in stream order
-int rf_enqueue(nid_pyr *p, const void *arg, hipStream_t st, const char *what) {
-  const RfCall &C = *static_cast<const RfCall *>(arg);
-  nid_ctx *c0 = p->ctx[0];
+// a fill call that fails behind rf_ensure: the planes may be half made (the reference is not ready either)
+int rf_failed(nid_pyr *p, int rc) {
+  p->rm.fill.have_uploaded = p->rm.fill.any_filled = false;
+  return rc;
+}
+
+int rf_failed(nid_pyr *p, const char *what, const char *step) { return rf_failed(p, rm_failed(p, what, step)); }
+
+// behind it pristine_dev is the reference's pristine depth, in stream order
+int rf_begin(nid_pyr *p, const char *what) {
+  int rc = rf_ensure(p);
+  if (rc) return rc;
+  if ((rc = rm_begin(p, what))) return rf_failed(p, rc);
   nid_pyr::RefMask &R = p->rm;
   nid_pyr::RefMask::Fill &F = R.fill;
-  const Geometry &g = c0->g;
-  const size_t N = (size_t)g.rows * g.cols;
-  auto failed = [&](const char *step) { return pyr_fail(p, NID_ERR_HIP, std::string(what) + ": " + step); };
+  const hipStream_t st = p->ctx[0]->stream;
+  const size_t N = (size_t)p->ctx[0]->g.rows * p->ctx[0]->g.cols;
   if (!F.have_uploaded) {  // (nothing is filled yet: the pristine depth is the uploaded one)
-    if (hipMemcpyAsync(F.uploaded_dev, R.pristine_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(uploaded)");
-    if (hipMemsetAsync(F.fill_dev, 0, 2 * N, st) != hipSuccess) return failed("hipMemsetAsync(fill)");
+    if (hipMemcpyAsync(F.uploaded_dev, R.pristine_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(uploaded)");
+    if (hipMemsetAsync(F.fill_dev, 0, 2 * N, st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(fill)");
   }
-  if (hipMemsetAsync(F.counts_dev, 0, 8 * sizeof(unsigned long long), st) != hipSuccess) return failed("hipMemsetAsync(fill counts)");
-  if (C.clear) {
-    if (hipMemsetAsync(F.fill_dev, 0, 2 * N, st) != hipSuccess) return failed("hipMemsetAsync(fill)");
-    if (hipMemcpyAsync(R.pristine_dev, F.uploaded_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(pristine)");
-  } else {
-    if (hipMemsetAsync(F.zbuf_dev, 0xFF, 4 * N, st) != hipSuccess) return failed("hipMemsetAsync(zbuf)");
-    hipLaunchKernelGGL(k_reffill_splat, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g, C.A, F.zbuf_dev.get(), F.counts_dev.get());
-    hipLaunchKernelGGL(k_reffill_apply, dim3((unsigned)((g.cols + kRmTileW - 1) / kRmTileW), (unsigned)((g.rows + kRmTileH - 1) / kRmTileH)), dim3(256),
-                       0, st, g.rows, g.cols, C.guard, C.guard_abs, C.guard_rel_1024, C.accumulate, F.zbuf_dev.get(), F.uploaded_dev.get(),
-                       R.ref_factor, F.fill_dev.get(), R.pristine_dev.get(), F.counts_dev.get());
-  }
-  if (hipMemcpyAsync(F.counts_host, F.counts_dev, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess) return failed("hipMemcpyAsync(fill counts)");
+  if (hipMemsetAsync(F.counts_dev, 0, 8 * sizeof(unsigned long long), st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(fill counts)");
   return NID_OK;
 }
 
-int rf_run(nid_pyr *p, const RfCall &C, nid_reffill_counts *out, const char *what) {
-  int rc = rf_ensure(p);
-  if (rc) return rc;
-  const RmBefore before = {rf_enqueue, &C};
-  nid_pyr::RefMask::Fill &F = p->rm.fill;
-  if ((rc = rm_run(p, RmFront::kKeep, nullptr, nullptr, 0, nullptr, what, &before))) {
-    F.have_uploaded = F.any_filled = false;  // (the planes may be half made; the reference is not ready either)
-    return rc;
-  }
+int rf_finish(nid_pyr *p, const char *what, nid_reffill_counts *out) {
+  nid_pyr::RefMask &R = p->rm;
+  nid_pyr::RefMask::Fill &F = R.fill;
+  const hipStream_t st = p->ctx[0]->stream;
+  const size_t N = (size_t)p->ctx[0]->g.rows * p->ctx[0]->g.cols;
+  if (hipMemcpyAsync(F.counts_host, F.counts_dev, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(fill counts)");
+  if (hipMemcpyAsync(R.work_dev, R.mask_dev, N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(work)");
+  const int rc = rm_finish(p, what, 0, nullptr);
+  if (rc) return rf_failed(p, rc);
   static_assert(sizeof(nid_reffill_counts) == 8 * sizeof(unsigned long long), "the totals are the record");
   nid_reffill_counts n;
   std::memcpy(&n, F.counts_host.host(), sizeof(n));
@@ -84,29 +76,46 @@ extern "C" {
 int nid_pyr_fill_reference_depth(nid_pyr *p, const double *pose7, int guard, int guard_abs, int guard_rel_1024, int accumulate,
                                  nid_reffill_counts *out) {
   if (!p || !pose7 || !rf::args_ok(guard, guard_abs, guard_rel_1024)) return NID_ERR_INVALID_ARG;
-  const int rc = rm_refuse(p, "nid_pyr_fill_reference_depth");
+  const char *what = "nid_pyr_fill_reference_depth";
+  int rc = rm_refuse(p, what);
   if (rc) return rc;
   if (!p->have_tdepth) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_fill_reference_depth: the target has no depth: nid_pyr_set_target_depth_u16() first");
   nid_ctx *c0 = p->ctx[0];
-  RfCall C = {};
+  nid_pyr::RefMask &R = p->rm;
+  nid_pyr::RefMask::Fill &F = R.fill;
+  RefFillArgs A = {};
   double Twc[16];  // the host's copy of the keyframe's matrix: where whatever made the reference staged it
   std::memcpy(Twc, c0->pair_stage + pair_stage_layout(c0->g).twc, sizeof(Twc));
-  rf::target_to_keyframe(Twc, pose7, C.A.M);
-  C.A.d1 = p->tdepth_dev;
-  C.A.factor1 = p->tdepth_factor;
-  C.A.factor0 = p->rm.ref_factor;
-  C.guard = guard; C.guard_abs = guard_abs; C.guard_rel_1024 = guard_rel_1024; C.accumulate = accumulate != 0;
-  return rf_run(p, C, out, "nid_pyr_fill_reference_depth");
+  rf::target_to_keyframe(Twc, pose7, A.M);
+  A.d1 = p->tdepth_dev;
+  A.factor1 = p->tdepth_factor;
+  A.factor0 = R.ref_factor;
+  if ((rc = rf_begin(p, what))) return rc;
+  const hipStream_t st = c0->stream;
+  const Geometry &g = c0->g;
+  const size_t N = (size_t)g.rows * g.cols;
+  if (hipMemsetAsync(F.zbuf_dev, 0xFF, 4 * N, st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(zbuf)");
+  hipLaunchKernelGGL(k_reffill_splat, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g, A, F.zbuf_dev.get(), F.counts_dev.get());
+  hipLaunchKernelGGL(k_reffill_apply, dim3((unsigned)((g.cols + kRmTileW - 1) / kRmTileW), (unsigned)((g.rows + kRmTileH - 1) / kRmTileH)), dim3(256),
+                     0, st, g.rows, g.cols, guard, guard_abs, guard_rel_1024, (int)(accumulate != 0), F.zbuf_dev.get(), F.uploaded_dev.get(),
+                     R.ref_factor, F.fill_dev.get(), R.pristine_dev.get(), F.counts_dev.get());
+  return rf_finish(p, what, out);
 }
 
 int nid_pyr_clear_reference_fill(nid_pyr *p) {
   if (!p) return NID_ERR_INVALID_ARG;
-  const int rc = rm_refuse(p, "nid_pyr_clear_reference_fill");
+  const char *what = "nid_pyr_clear_reference_fill";
+  int rc = rm_refuse(p, what);
   if (rc) return rc;
-  if (!p->rm.fill.have_uploaded || !p->rm.fill.any_filled) return NID_OK;  // nothing is filled
-  RfCall C = {};
-  C.clear = true;
-  return rf_run(p, C, nullptr, "nid_pyr_clear_reference_fill");
+  nid_pyr::RefMask &R = p->rm;
+  nid_pyr::RefMask::Fill &F = R.fill;
+  if (!F.have_uploaded || !F.any_filled) return NID_OK;  // nothing is filled
+  if ((rc = rf_begin(p, what))) return rc;
+  const hipStream_t st = p->ctx[0]->stream;
+  const size_t N = (size_t)p->ctx[0]->g.rows * p->ctx[0]->g.cols;
+  if (hipMemsetAsync(F.fill_dev, 0, 2 * N, st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(fill)");
+  if (hipMemcpyAsync(R.pristine_dev, F.uploaded_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(pristine)");
+  return rf_finish(p, what, nullptr);
 }
 
 int nid_pyr_get_reference_fill_u16(nid_pyr *p, uint16_t *out) {
@@ -131,11 +140,9 @@ int nid_reffill_host(const nid_config *cfg, const uint16_t *depth0_u16, double f
                      nid_reffill_counts *counts) {
   if (!cfg || !depth0_u16 || !Twc || !depth1_u16 || !pose7 || !fill_inout || !rf::args_ok(guard, guard_abs, guard_rel_1024)) return NID_ERR_INVALID_ARG;
   if (cfg->rows < 1 || cfg->cols < 1 || (int64_t)cfg->rows * cfg->cols > INT32_MAX) return NID_ERR_INVALID_ARG;
-  rf::Splat S;
-  rf::target_to_keyframe(Twc, pose7, S.M);
-  S.fx = cfg->fx; S.fy = cfg->fy; S.cx = cfg->cx; S.cy = cfg->cy;
-  S.rows = cfg->rows; S.cols = cfg->cols;
-  S.d1 = depth1_u16; S.factor1 = factor1; S.factor0 = factor0;
+  double M[12];
+  rf::target_to_keyframe(Twc, pose7, M);
+  const rf::Splat S = rf::make_splat(*cfg, M, depth1_u16, factor1, factor0);
   std::vector<uint32_t> zbuf;
   try {
     zbuf.resize((size_t)cfg->rows * (size_t)cfg->cols);

@@ -32,6 +32,17 @@ struct Splat {
   double factor1, factor0;
 };
 
+// the Splat of a call's matrix M, an image geometry g (Geometry on the device, nid_config on the host) and its arguments
+template <class G>
+NID_DC_HD Splat make_splat(const G &g, const double *M, const uint16_t *d1, double factor1, double factor0) {
+  Splat S;
+  for (int k = 0; k < 12; k++) S.M[k] = M[k];
+  S.fx = g.fx; S.fy = g.fy; S.cx = g.cx; S.cy = g.cy;
+  S.rows = g.rows; S.cols = g.cols;
+  S.d1 = d1; S.factor1 = factor1; S.factor0 = factor0;
+  return S;
+}
+
 // M: x_k = T_cw(keyframe) T_wc(target) x_t from the keyframe's column-major camera -> world matrix and the target's
 // world -> camera pose7.  Host only, once per call: the device call and the host twin read the same twelve doubles.
 inline void target_to_keyframe(const double *Twc16, const double *pose7, double *M) {

@@ -1,25 +1,16 @@
 // nid_refmask.inc -- the per-pixel mask on the resident pyramid's reference and the tracker's use of it
 // (include/nid/nid_refmask.h).  Part of nid_capi.hip's translation unit (included behind nid_keyframe.inc).
 //
-// The three masking calls are ONE chain on level 0's stream with three ways to its front: the pristine copy and a zero
-// plane if this is the first call behind a new reference; the classified bytes into work_dev -- the caller's plane
-// uploaded (nid_pyr_set_reference_mask_u8), zeros (nid_pyr_clear_reference_mask) or k_refmask_classify
-// (nid_pyr_mask_occluded) --; then k_refmask_dilate_apply (the final plane, level 0's masked depth, the counts), the
-// REFERENCE half of a promotion from there on (k_pyr_down_depth per coarser level, pair_u16_device_ref per level:
-// nid_pyr_stream.inc) and the counts' way home.  They open and close like the frame operations and leave every level as a
-// promotion does.  No evaluation kernel is launched, no SlotArgs filled, no slot touched.
-// nid_reffill.inc (behind this file) runs the same chain with a fourth front -- the plane as it is -- and its own kernels
-// between the pristine copy and the front (RmBefore): there the pristine depth is what a fill makes of the uploaded one.
+// A masking call is straight-line code on level 0's stream in nid_pyr.inc's frame: rm_begin (pyr_open over the reference;
+// the pristine copy and a zero plane if this is the first call behind a new reference; the counts zeroed), the call's own
+// MIDDLE -- the classified bytes into work_dev: the caller's plane uploaded (nid_pyr_set_reference_mask_u8), zeros
+// (nid_pyr_clear_reference_mask) or k_refmask_classify (nid_pyr_mask_occluded) --, and rm_finish (k_refmask_dilate_apply:
+// the final plane, level 0's masked depth, the counts; pyr_ref_tail; the counts' way home; pyr_close), which leaves every
+// level as a promotion does.  No evaluation kernel is launched, no SlotArgs filled, no slot touched.
+// nid_reffill.inc (behind this file) puts its own operations between the same two: there the pristine depth is what a fill
+// makes of the uploaded one, and the plane goes into work_dev as it is.
 
 namespace {
-
-enum class RmFront { kCallerPlane, kZeros, kClassify, kKeep };  // (kKeep: the plane as it is -- nid_reffill.inc's front)
-
-// what a call puts between the pristine copy and the front (nid_reffill.inc: the kernels that rewrite pristine_dev)
-struct RmBefore {
-  int (*enqueue)(nid_pyr *p, const void *arg, hipStream_t st, const char *what);  // NID_OK, or the error behind pyr_fail
-  const void *arg;
-};
 
 int rm_ensure(nid_pyr *p, bool plane_host) {
   nid_ctx *c0 = p->ctx[0];
@@ -40,59 +31,41 @@ int rm_refuse(nid_pyr *p, const char *what) {
   return pyr_refuse_pending(p, what);
 }
 
-// the chain; A: k_refmask_classify's arguments but the planes (kClassify only), caller: the plane of kCallerPlane
-int rm_run(nid_pyr *p, RmFront front, const RefMaskArgs *A, const uint8_t *caller, int dilate, nid_refmask_counts *out, const char *what,
-           const RmBefore *before = nullptr) {
+// an error between rm_begin and rm_finish: nothing of the call stays in flight
+int rm_failed(nid_pyr *p, const char *what, const char *step) {
+  return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, std::string(what) + ": " + step));
+}
+
+int rm_begin(nid_pyr *p, const char *what, bool plane_host = false) {
+  int rc = pyr_open(p, what, kPyrRef);  // (the resident reference made again, not a new one: its mask and fill stay)
+  if (rc) return rc;
+  if ((rc = rm_ensure(p, plane_host))) return rc;  // (nothing enqueued yet)
   nid_ctx *c0 = p->ctx[0];
   nid_pyr::RefMask &R = p->rm;
-  // from here on the reference is being overwritten: no level has one until the stream has drained
-  p->have_pair = false;
-  for (int l = 0; l < p->levels; l++) p->ctx[l]->have_ref = p->ctx[l]->have_href = false;
-  int rc = pyr_front(p);
-  if (rc) return rc;
-  if ((rc = rm_ensure(p, front == RmFront::kCallerPlane))) return rc;  // (nothing enqueued yet)
+  const hipStream_t st = c0->stream;
+  const size_t N = (size_t)c0->g.rows * c0->g.cols;
+  if (!R.have_pristine) {
+    if (hipMemcpyAsync(R.pristine_dev, c0->depth16_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rm_failed(p, what, "hipMemcpyAsync(pristine)");
+    if (hipMemsetAsync(R.mask_dev, 0, N, st) != hipSuccess) return rm_failed(p, what, "hipMemsetAsync(mask)");
+  }
+  if (hipMemsetAsync(R.counts_dev, 0, 8 * sizeof(unsigned long long), st) != hipSuccess) return rm_failed(p, what, "hipMemsetAsync(counts)");
+  return NID_OK;
+}
+
+// work_dev holds the call's classified bytes, in stream order
+int rm_finish(nid_pyr *p, const char *what, int dilate, nid_refmask_counts *out) {
+  nid_ctx *c0 = p->ctx[0];
+  nid_pyr::RefMask &R = p->rm;
   const hipStream_t st = c0->stream;
   const Geometry &g = c0->g;
-  const size_t N = (size_t)g.rows * g.cols;
-  auto failed = [&](const char *step) { return pyr_drain(p, pyr_fail(p, NID_ERR_HIP, std::string(what) + ": " + step)); };
-  if (!R.have_pristine) {
-    if (hipMemcpyAsync(R.pristine_dev, c0->depth16_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(pristine)");
-    if (hipMemsetAsync(R.mask_dev, 0, N, st) != hipSuccess) return failed("hipMemsetAsync(mask)");
-  }
-  if (hipMemsetAsync(R.counts_dev, 0, 8 * sizeof(unsigned long long), st) != hipSuccess) return failed("hipMemsetAsync(counts)");
-  if (before && (rc = before->enqueue(p, before->arg, st, what))) return pyr_drain(p, rc);
-  if (front == RmFront::kCallerPlane) {
-    uint8_t *h = R.plane_host;
-    for (size_t i = 0; i < N; i++) h[i] = caller[i] ? NID_REFMASK_CALLER : 0;
-    if (hipMemcpyAsync(R.work_dev, h, N, hipMemcpyHostToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(mask)");
-  } else if (front == RmFront::kZeros) {
-    if (hipMemsetAsync(R.work_dev, 0, N, st) != hipSuccess) return failed("hipMemsetAsync(work)");
-  } else if (front == RmFront::kKeep) {  // (a final plane through dc::mask_final with dilate 0 is itself)
-    if (hipMemcpyAsync(R.work_dev, R.mask_dev, N, hipMemcpyDeviceToDevice, st) != hipSuccess) return failed("hipMemcpyAsync(work)");
-  } else {
-    RefMaskArgs a = *A;
-    a.d0 = R.pristine_dev; a.Twc = c0->Twc_dev; a.d1 = p->tdepth_dev;
-    a.factor0 = R.ref_factor; a.factor1 = p->tdepth_factor;
-    hipLaunchKernelGGL(k_refmask_classify, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g, a, R.mask_dev.get(), R.work_dev.get());
-  }
   hipLaunchKernelGGL(k_refmask_dilate_apply, dim3((unsigned)((g.cols + kRmTileW - 1) / kRmTileW), (unsigned)((g.rows + kRmTileH - 1) / kRmTileH)), dim3(256),
                      0, st, g.rows, g.cols, dilate, R.work_dev.get(), R.pristine_dev.get(), R.ref_factor, R.mask_dev.get(), c0->depth16_dev.get(),
                      R.counts_dev.get());
-  for (int l = 1; l < p->levels; l++) {
-    nid_ctx *src = p->ctx[l - 1], *dst = p->ctx[l];
-    hipLaunchKernelGGL(k_pyr_down_depth, dim3(pyr_down_blocks(dst)), dim3(256), 0, st, dst->g.rows, dst->g.cols, src->depth16_dev, R.ref_factor,
-                       dst->depth16_dev);
-  }
-  for (int l = 0; l < p->levels; l++) pair_u16_device_ref(p->ctx[l], R.ref_factor, st);
-  if (hipGetLastError() != hipSuccess) return failed("a launch failed");
-  if (hipMemcpyAsync(R.counts_host, R.counts_dev, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess) return failed("hipMemcpyAsync(counts)");
-  if ((rc = pyr_finish(p, what))) return rc;
-  for (int l = 0; l < p->levels; l++) {
-    nid_ctx *ctx = p->ctx[l];
-    ctx->have_ref = true;  // (have_href stays false: the reference stage is the caller's)
-    ctx->ref_from_depth = true;
-  }
-  p->have_pair = true;
+  pyr_ref_tail(p, R.ref_factor, st);
+  if (hipGetLastError() != hipSuccess) return rm_failed(p, what, "a launch failed");
+  if (hipMemcpyAsync(R.counts_host, R.counts_dev, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess) return rm_failed(p, what, "hipMemcpyAsync(counts)");
+  const int rc = pyr_close(p, what, kPyrRef);
+  if (rc) return rc;
   R.have_pristine = true;
   const unsigned long long *n = R.counts_host;
   R.any_masked = n[kRmCountWords - 1] != 0;
@@ -109,32 +82,50 @@ extern "C" {
 
 int nid_pyr_set_reference_mask_u8(nid_pyr *p, const uint8_t *mask) {
   if (!p || !mask) return NID_ERR_INVALID_ARG;
-  const int rc = rm_refuse(p, "nid_pyr_set_reference_mask_u8");
+  const char *what = "nid_pyr_set_reference_mask_u8";
+  int rc = rm_refuse(p, what);
   if (rc) return rc;
-  return rm_run(p, RmFront::kCallerPlane, nullptr, mask, 0, nullptr, "nid_pyr_set_reference_mask_u8");
+  if ((rc = rm_begin(p, what, true))) return rc;
+  nid_pyr::RefMask &R = p->rm;
+  const size_t N = (size_t)p->ctx[0]->g.rows * p->ctx[0]->g.cols;
+  uint8_t *h = R.plane_host;
+  for (size_t i = 0; i < N; i++) h[i] = mask[i] ? NID_REFMASK_CALLER : 0;
+  if (hipMemcpyAsync(R.work_dev, h, N, hipMemcpyHostToDevice, p->ctx[0]->stream) != hipSuccess) return rm_failed(p, what, "hipMemcpyAsync(mask)");
+  return rm_finish(p, what, 0, nullptr);
 }
 
 int nid_pyr_mask_occluded(nid_pyr *p, const double *pose7, double tol_abs, double tol_rel, int classes, int dilate, int accumulate,
                           nid_refmask_counts *out) {
   if (!p || !pose7 || !dc::refmask_args_ok(tol_abs, tol_rel, classes, dilate)) return NID_ERR_INVALID_ARG;
-  int rc = rm_refuse(p, "nid_pyr_mask_occluded");
+  const char *what = "nid_pyr_mask_occluded";
+  int rc = rm_refuse(p, what);
   if (rc) return rc;
   if (!p->have_tdepth) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_mask_occluded: the target has no depth: nid_pyr_set_target_depth_u16() first");
+  if ((rc = rm_begin(p, what))) return rc;
+  nid_ctx *c0 = p->ctx[0];
+  nid_pyr::RefMask &R = p->rm;
   RefMaskArgs A = {};
   double q7[7];
   int32_t mode;
-  lm::pose_record(pose7, p->ctx[0]->xform, q7, A.M, &mode);
-  A.tol_abs = tol_abs; A.tol_rel = tol_rel;
+  lm::pose_record(pose7, c0->xform, q7, A.M, &mode);
+  A.d0 = R.pristine_dev; A.Twc = c0->Twc_dev; A.d1 = p->tdepth_dev;
+  A.factor0 = R.ref_factor; A.factor1 = p->tdepth_factor; A.tol_abs = tol_abs; A.tol_rel = tol_rel;
   A.classes = classes; A.accumulate = accumulate != 0;
-  return rm_run(p, RmFront::kClassify, &A, nullptr, dilate, out, "nid_pyr_mask_occluded");
+  const size_t N = (size_t)c0->g.rows * c0->g.cols;
+  hipLaunchKernelGGL(k_refmask_classify, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c0->stream, c0->g, A, R.mask_dev.get(), R.work_dev.get());
+  return rm_finish(p, what, dilate, out);
 }
 
 int nid_pyr_clear_reference_mask(nid_pyr *p) {
   if (!p) return NID_ERR_INVALID_ARG;
-  const int rc = rm_refuse(p, "nid_pyr_clear_reference_mask");
+  const char *what = "nid_pyr_clear_reference_mask";
+  int rc = rm_refuse(p, what);
   if (rc) return rc;
   if (!p->rm.have_pristine || !p->rm.any_masked) return NID_OK;  // nothing is masked
-  return rm_run(p, RmFront::kZeros, nullptr, nullptr, 0, nullptr, "nid_pyr_clear_reference_mask");
+  if ((rc = rm_begin(p, what))) return rc;
+  const size_t N = (size_t)p->ctx[0]->g.rows * p->ctx[0]->g.cols;
+  if (hipMemsetAsync(p->rm.work_dev, 0, N, p->ctx[0]->stream) != hipSuccess) return rm_failed(p, what, "hipMemsetAsync(work)");
+  return rm_finish(p, what, 0, nullptr);
 }
 
 int nid_pyr_get_reference_mask_u8(nid_pyr *p, uint8_t *out) {
@@ -159,13 +150,10 @@ int nid_refmask_host(const nid_config *cfg, const uint16_t *depth0_u16, double f
                      uint8_t *mask_inout, nid_refmask_counts *counts) {
   if (!cfg || !depth0_u16 || !Twc || !depth1_u16 || !pose7 || !mask_inout || !dc::refmask_args_ok(tol_abs, tol_rel, classes, dilate)) return NID_ERR_INVALID_ARG;
   if (cfg->rows < 1 || cfg->cols < 1 || (int64_t)cfg->rows * cfg->cols > INT32_MAX) return NID_ERR_INVALID_ARG;
-  dc::View V;
-  double q7[7];
+  double q7[7], M[12];
   int32_t mode;
-  lm::pose_record(pose7, NID_XFORM_QUAT, q7, V.M, &mode);
-  V.fx = cfg->fx; V.fy = cfg->fy; V.cx = cfg->cx; V.cy = cfg->cy;
-  V.rows = cfg->rows; V.cols = cfg->cols;
-  V.d1 = depth1_u16; V.factor = factor1; V.tol_abs = tol_abs; V.tol_rel = tol_rel;
+  lm::pose_record(pose7, NID_XFORM_QUAT, q7, M, &mode);
+  const dc::View V = dc::make_view(*cfg, M, depth1_u16, factor1, tol_abs, tol_rel);
   const dc::Keyframe K = {depth0_u16, factor0, Twc};
   dc::refmask_host(V, K, classes, dilate, accumulate != 0, mask_inout, counts);
   return NID_OK;

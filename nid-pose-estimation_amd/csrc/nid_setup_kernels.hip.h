@@ -220,12 +220,7 @@ static_assert(offsetof(nid_depth_counts, sum_abs_um) == 48, "a total is the cell
 __global__ void __launch_bounds__(256) k_depth_check(Geometry g, Tiles t, DepthCheckArgs A) {
   __shared__ unsigned long long part[4][8];
   const int cl = (int)(blockIdx.x % (unsigned)g.nloc), pose = (int)(blockIdx.x / (unsigned)g.nloc), tid = threadIdx.x;
-  dc::View V;
-#pragma unroll
-  for (int k = 0; k < 12; k++) V.M[k] = A.M[(size_t)pose * 12 + k];
-  V.fx = g.fx; V.fy = g.fy; V.cx = g.cx; V.cy = g.cy;
-  V.rows = g.rows; V.cols = g.cols;
-  V.d1 = A.d1; V.factor = A.factor; V.tol_abs = A.tol_abs; V.tol_rel = A.tol_rel;
+  const dc::View V = dc::make_view(g, A.M + (size_t)pose * 12, A.d1, A.factor, A.tol_abs, A.tol_rel);
   nid_depth_cell a = {};
   const size_t base = (size_t)cl * g.pstride;
   for (int s = tid; s < g.pstride; s += 256) dc::sample(V, t.X[base + s], t.Y[base + s], t.Z[base + s], &a);
@@ -252,6 +247,29 @@ __global__ void __launch_bounds__(256) k_depth_check(Geometry g, Tiles t, DepthC
   }
 }
 
+// The int counts of a 256-lane workgroup into a call's totals (the mask's and the fill's kernels): each of a lane's K counts
+// summed over the wave with shuffles, the four waves' sums through `part` in LDS behind ONE barrier -- every lane of the
+// workgroup calls this --, and lanes 0 .. K - 1 add the workgroup's sums to words Off .. Off + K - 1 of `totals` with ONE
+// 64-bit INTEGER atomic each (exact, order-independent).  The counts come as scalar arguments: behind a reference to an
+// array of them the compiler kept the callers' pixel-loop counters in 64 bits (7 and 4 more VGPRs).
+template <int Off, int W, class... Ints>
+__device__ __forceinline__ void counts_to_totals(unsigned long long (&part)[4][W], int tid, unsigned long long *totals, Ints... counts) {
+  constexpr int K = (int)sizeof...(Ints);
+  int cnt[K] = {counts...};
+  static_assert(K <= W && Off + K <= 8, "a wave's row of part, the totals' eight words");
+#pragma unroll
+  for (int o = 32; o; o >>= 1) {
+#pragma unroll
+    for (int k = 0; k < K; k++) cnt[k] += __shfl_down(cnt[k], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; k++) part[tid >> 6][k] = (unsigned long long)cnt[k];
+  }
+  __syncthreads();
+  if (tid < K) atomicAdd(totals + Off + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+}
+
 // The reference mask (nid/nid_refmask.h), two kernels behind each other on one stream.
 //
 // k_refmask_classify: image order, one lane per pixel of level 0 -- the pristine u16 depth and the u8 plane are read and
@@ -272,12 +290,7 @@ static_assert(sizeof(nid_refmask_counts) == 64, "nid_refmask.h's record");
 __global__ void __launch_bounds__(256) k_refmask_classify(Geometry g, RefMaskArgs A, const uint8_t *__restrict__ mask, uint8_t *__restrict__ work) {
   const long id = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= (long)g.rows * g.cols) return;
-  dc::View V;
-#pragma unroll
-  for (int k = 0; k < 12; k++) V.M[k] = A.M[k];
-  V.fx = g.fx; V.fy = g.fy; V.cx = g.cx; V.cy = g.cy;
-  V.rows = g.rows; V.cols = g.cols;
-  V.d1 = A.d1; V.factor = A.factor1; V.tol_abs = A.tol_abs; V.tol_rel = A.tol_rel;
+  const dc::View V = dc::make_view(g, A.M, A.d1, A.factor1, A.tol_abs, A.tol_rel);
   const dc::Keyframe K = {A.d0, A.factor0, A.Twc};
   work[id] = dc::mask_classified(V, K, (int)(id / g.cols), (int)(id % g.cols), mask[id], A.classes, A.accumulate);
 }
@@ -335,18 +348,7 @@ __global__ void __launch_bounds__(256) k_refmask_dilate_apply(int rows, int cols
     dc::mask_count(b, dc::depth_valid(z, factor), &n);
     nonzero += b != 0;
   }
-  int cnt[kRmCountWords] = {(int)n.n_valid, (int)n.n_caller, (int)n.n_occluded, (int)n.n_through, (int)n.n_dilated, (int)n.n_masked, nonzero};
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kRmCountWords; k++) cnt[k] += __shfl_down(cnt[k], o, 64);
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kRmCountWords; k++) part[tid >> 6][k] = (unsigned long long)cnt[k];
-  }
-  __syncthreads();
-  if (tid < kRmCountWords) atomicAdd(totals + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+  counts_to_totals<0>(part, tid, totals, (int)n.n_valid, (int)n.n_caller, (int)n.n_occluded, (int)n.n_through, (int)n.n_dilated, (int)n.n_masked, nonzero);
 }
 
 // The reference fill (nid/nid_reffill.h), two kernels behind each other on one stream, in front of the masking calls' chain.
@@ -370,12 +372,7 @@ __global__ void __launch_bounds__(256) k_reffill_splat(Geometry g, RefFillArgs A
   const long id = (long)blockIdx.x * blockDim.x + tid;
   int cnt[2] = {0, 0};
   if (id < (long)g.rows * g.cols) {
-    rf::Splat S;
-#pragma unroll
-    for (int k = 0; k < 12; k++) S.M[k] = A.M[k];
-    S.fx = g.fx; S.fy = g.fy; S.cx = g.cx; S.cy = g.cy;
-    S.rows = g.rows; S.cols = g.cols;
-    S.d1 = A.d1; S.factor1 = A.factor1; S.factor0 = A.factor0;
+    const rf::Splat S = rf::make_splat(g, A.M, A.d1, A.factor1, A.factor0);
     size_t idx = 0;
     uint32_t q = 0;
     const int k = rf::splat(S, (int)(id / g.cols), (int)(id % g.cols), &idx, &q);
@@ -383,17 +380,7 @@ __global__ void __launch_bounds__(256) k_reffill_splat(Geometry g, RefFillArgs A
     cnt[1] = k == 2;
     if (k == 2) atomicMin(zbuf + idx, q);  // (idx < rows cols: rf::splat's frame test)
   }
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-    cnt[0] += __shfl_down(cnt[0], o, 64);
-    cnt[1] += __shfl_down(cnt[1], o, 64);
-  }
-  if ((tid & 63) == 0) {
-    part[tid >> 6][0] = (unsigned long long)cnt[0];
-    part[tid >> 6][1] = (unsigned long long)cnt[1];
-  }
-  __syncthreads();
-  if (tid < 2) atomicAdd(totals + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+  counts_to_totals<0>(part, tid, totals, cnt[0], cnt[1]);
 }
 
 // k_reffill_apply: ONE workgroup per kRmTileH x kRmTileW image tile, a wave per tile row, as k_refmask_dilate_apply.  The
@@ -403,7 +390,6 @@ __global__ void __launch_bounds__(256) k_reffill_splat(Geometry g, RefFillArgs A
 // pristine depth fill-or-uploaded for the masking chain behind this kernel, and the pixel's five counts -- summed like the
 // mask's and added to words 2 .. 6 of the call's totals with ONE 64-bit INTEGER atomic each.
 constexpr int kRfHalo = NID_REFFILL_MAX_GUARD;
-constexpr int kRfCountWords = 5;  // n_hit, n_holes, n_refused, n_new, n_filled
 
 __global__ void __launch_bounds__(256) k_reffill_apply(int rows, int cols, int guard, int guard_abs, int guard_rel_1024, int accumulate,
                                                        const uint32_t *__restrict__ zbuf, const uint16_t *__restrict__ uploaded, double factor0,
@@ -448,18 +434,7 @@ __global__ void __launch_bounds__(256) k_reffill_apply(int rows, int cols, int g
     fill[i] = f;
     pristine[i] = f ? f : up;
   }
-  int cnt[kRfCountWords] = {(int)n.n_hit, (int)n.n_holes, (int)n.n_refused, (int)n.n_new, (int)n.n_filled};
-#pragma unroll
-  for (int o = 32; o; o >>= 1) {
-#pragma unroll
-    for (int k = 0; k < kRfCountWords; k++) cnt[k] += __shfl_down(cnt[k], o, 64);
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kRfCountWords; k++) part[tid >> 6][k] = (unsigned long long)cnt[k];
-  }
-  __syncthreads();
-  if (tid < kRfCountWords) atomicAdd(totals + 2 + tid, part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]);
+  counts_to_totals<2>(part, tid, totals, (int)n.n_hit, (int)n.n_holes, (int)n.n_refused, (int)n.n_new, (int)n.n_filled);
 }
 
 // depth pixels that belong to no cell (rows/cols not divisible by cell_num, Q11)

@@ -214,3 +214,24 @@ def test_three_flat_iterations_end_with_nbad_and_a_finished_chain_is_frozen(capi
         for blk in (block(H, b, 1.0), block(2 * H, -b, np.nan), np.full(32, np.inf)):
             assert not capi.lm_step_host(fin, blk)
             assert snapshot(fin) == snap, "a finished chain changed"
+
+
+def test_rank_rule_alone_under_the_host_sanitizers(tmp_path):
+    """tests/cpp/rank_chains_check.cpp: lm::rank_chains (csrc/nid_lm_step.h) alone in a program of its own, built with
+    -fsanitize=address,undefined (runtimes linked statically: nothing of the environment is involved), against a selection
+    sort over (chi2 / n_active, index): ties, n_active == 0, NaN / inf chi2, nothing eligible, an empty batch, and 4000
+    random batches over a handful of values."""
+    import os
+    import re
+    import subprocess
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "rank_chains_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan",
+                           "-I", os.path.join(root, "include"), "-I", os.path.join(root, "nid-pose-estimation_amd", "csrc"),
+                           "-o", exe, os.path.join(root, "tests", "cpp", "rank_chains_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-4000:])
+    m = re.search(r"rank chains: (\d+) cases, (\d+) ties among ranked neighbours, 0 failures", r.stdout)
+    assert m and int(m.group(1)) >= 4000 and int(m.group(2)) >= 4000, r.stdout
