@@ -28,44 +28,40 @@
 //     In both modes a new frame pair (new buffers, or CudaComputeHref) is noticed at once, and
 //     nid_legacy_invalidate(parts) makes the next call recompute the named parts' hashes in full.
 //     NID_LEGACY_ALWAYS_UPLOAD=1 uploads everything on every call.
+// The watch itself -- keys, hashes, the pool of worker threads, the verification of one call -- is nid_buffer_watch.h
+// (checked alone: tests/cpp/buffer_watch_check.cpp); here: which mode asks what of it, the device session, the operators.
 #include "nid/legacy_ops.h"
 
-#include <atomic>
-#include <chrono>
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <functional>
-#include <memory>
-#include <mutex>
-#include <pthread.h>
-#include <thread>
-#include <unistd.h>
 #include <vector>
 
 #include "nid/nid_c.h"
 #include "nid/nid_multi.h"
+#include "nid_buffer_watch.h"
 
 namespace {
 
-constexpr int kSlices = NID_LEGACY_SLICES;   // a big buffer's content key: one hash per slice; the default mode checks one slice per call
+using namespace nid_watch;
+static_assert(kSlices == NID_LEGACY_SLICES, "nid_buffer_watch.h restates the slice count of legacy_ops.h");
+
+// what a context is created for
+struct PairShape {
+  int rows = 0, cols = 0, cell = 0, bins = 0;
+  double intr[4] = {0, 0, 0, 0};
+  bool operator==(const PairShape &o) const {
+    return rows == o.rows && cols == o.cols && cell == o.cell && bins == o.bins && std::equal(intr, intr + 4, o.intr);
+  }
+};
 
 struct LegacyState {
   nid_multi *m = nullptr;
-  int rows = 0, cols = 0, cell = 0, bins = 0;
-  double intr[4] = {0, 0, 0, 0};
+  PairShape shape;
   // keys of what is resident on the device(s)
-  struct Key {
-    const void *addr = nullptr;
-    size_t n = 0;             // elements
-    uint64_t quick = 0, full = 0;
-    uint64_t slice[kSlices] = {};  // big buffers: the slices' hashes (`full` is their combination)
-    bool valid = false;
-    bool full_known = true;   // false: the hashes were never taken -- a full check then counts as "changed"
-  };
   Key k_im0, k_points, k_im1, k_bs_ref, k_counter, k_href;
   bool have_ref = false, have_target = false, have_href = false;
   unsigned long calls = 0;      // CudaComputeH calls on this frame pair (CudaComputeHref starts a new count)
@@ -148,267 +144,15 @@ bool always_upload() {
   return v;
 }
 
-// 64 samples spread over the array + its length, FNV-1a over their bytes (never 0)
-template <typename T>
-uint64_t fingerprint(const T *a, size_t n) {
-  if (!a) return 1;
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void *p, size_t bytes) {
-    const unsigned char *b = static_cast<const unsigned char *>(p);
-    for (size_t i = 0; i < bytes; i++) { h ^= b[i]; h *= 1099511628211ull; }
-  };
-  mix(&n, sizeof(n));
-  const size_t samples = n < 64 ? n : 64;
-  for (size_t k = 0; k < samples; k++) {
-    const size_t i = samples > 1 ? (size_t)((unsigned __int128)k * (n - 1) / (samples - 1)) : 0;
-    mix(&a[i], sizeof(T));
-  }
-  return h ? h : 2;
-}
-
-// ---- content hashes -------------------------------------------------------------------------------------------
-// A frame pair's big buffers (points3d 7.4 MB, bs_value 9.8 MB at 640x480) are hashed once per pair in full and one
-// slice per call after that; one core does ~20 GB/s.  The slices go to a small pool of worker threads (created at the
-// first use, parked on a condition variable in between) beside the caller.  The pool's size: NID_LEGACY_HASH_THREADS
-// workers (default 3; 0: the caller hashes alone, no thread is created).  A job lives INSIDE one operator call: start()
-// takes the pool, finish() -- always before the operator returns -- gives it back; no worker touches a caller buffer
-// outside start() .. finish().
-class HashPool {
- public:
-  static HashPool &get() { static HashPool *p = new HashPool;  return *p; }  // (never destroyed: its parked workers end with the process)
-  // start(n, job): job(0..n-1) is handed to the workers -- each takes the next part that nobody has taken -- and the
-  // call returns; finish(): the caller takes what is left and waits for the rest.  One job at a time, started and
-  // finished by the same thread; the job must stay valid until finish().
-  // Parts are claimed with one atomic increment on the JOB's own counter (a worker that comes late holds the old job
-  // object and finds nothing left in it: it can never touch the next job's parts); the mutex is for parking only.
-  void start(int nparts, std::function<void(int)> fn) {
-    call_.lock();
-    auto j = std::make_shared<Job>();
-    j->fn = std::move(fn);
-    j->nparts = nparts;
-    j->remaining.store(nparts, std::memory_order_relaxed);
-    mine_ = j;
-    std::atomic_store(&current_, j);
-    generation_.fetch_add(1);  // (sequentially consistent with parked_: either this thread sees a parking worker, or the worker sees the new generation)
-    if (parked_.load() > 0 && has_workers()) {  // (a fork()ed child has no workers: finish() does all parts)
-      std::lock_guard<std::mutex> g(m_);
-      wake_.notify_all();
-    }
-  }
-  void finish() {
-    Job &j = *mine_;
-    help(j);
-    while (j.remaining.load(std::memory_order_acquire) > 0) __builtin_ia32_pause();  // (parts in other threads' hands: microseconds)
-    std::atomic_store(&current_, std::shared_ptr<Job>());
-    mine_.reset();
-    call_.unlock();
-  }
-  void run(int nparts, std::function<void(int)> job) { start(nparts, std::move(job)); finish(); }
-  bool has_workers() const { return !workers_.empty() && getpid() == owner_; }
-
- private:
-  struct Job {
-    std::function<void(int)> fn;
-    int nparts = 0;
-    std::atomic<int> next{0}, remaining{0};
-  };
-  HashPool() : owner_(getpid()) {
-    int n = 3;
-    if (const char *e = getenv("NID_LEGACY_HASH_THREADS")) n = std::max(0, std::min(15, atoi(e)));
-    if (const char *e = getenv("NID_LEGACY_HASH_SPIN_US")) spin_us_ = std::max(0, std::min(100000, atoi(e)));
-    for (int w = 0; w < n; w++) workers_.emplace_back([this] { loop(); });
-    // fork(): threads do not survive it, locks do -- a child forked while a worker held m_ would wait for it for ever.
-    // The prepare handler takes call_ (free whenever no operator is inside start() .. finish(): a job never outlives
-    // the call that started it, so a fork() between two calls finds it free; a fork() from another thread waits for
-    // the running call's finish()) and then m_, so the child inherits both free, with no job in flight (and finds
-    // itself without workers by its pid).
-    pthread_atfork([] { HashPool &p = get(); p.call_.lock(); p.m_.lock(); },
-                   [] { HashPool &p = get(); p.m_.unlock(); p.call_.unlock(); },
-                   [] { HashPool &p = get(); p.m_.unlock(); p.call_.unlock(); });
-  }
-  static void help(Job &j) {  // take parts until none is left
-    for (;;) {
-      const int part = j.next.fetch_add(1, std::memory_order_acq_rel);
-      if (part >= j.nparts) return;
-      j.fn(part);
-      j.remaining.fetch_sub(1, std::memory_order_release);
-    }
-  }
-  // A worker that has just served a job keeps POLLING for the next one for spin_us_ microseconds before it parks on the
-  // condition variable: the operators are called back to back by the LM (one call per 30-60 us), and a parked thread
-  // takes 10-20 us to come back -- as long as the whole evaluation it is supposed to hide behind
-  // (profiles/r06_legacy_call_cost.txt).  NID_LEGACY_HASH_SPIN_US (default 150; 0: park at once).
-  void loop() {
-    unsigned long seen = 0;
-    for (;;) {
-      const auto t0 = std::chrono::steady_clock::now();
-      bool got = false;
-      for (unsigned spins = 0; spin_us_ > 0; spins++) {
-        if (generation_.load(std::memory_order_acquire) != seen) { got = true; break; }
-        __builtin_ia32_pause();
-        if ((spins & 63) == 63 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us_)) break;
-      }
-      if (!got) {
-        std::unique_lock<std::mutex> g(m_);
-        parked_.fetch_add(1);
-        wake_.wait(g, [&] { return generation_.load() != seen; });
-        parked_.fetch_sub(1);
-      }
-      seen = generation_.load(std::memory_order_acquire);
-      if (std::shared_ptr<Job> j = std::atomic_load(&current_)) help(*j);
-    }
-  }
-  std::mutex call_, m_;
-  std::condition_variable wake_;
-  std::shared_ptr<Job> current_, mine_;
-  std::vector<std::thread> workers_;
-  std::atomic<unsigned long> generation_{0};
-  std::atomic<int> parked_{0};
-  int spin_us_ = 150;
-  const pid_t owner_;
-};
-
-// one contiguous run of bytes, 64 bits: eight interleaved multiply-xor lanes over the 8-byte words (eight independent
-// dependency chains keep the multiplier busy: memory-bound, ~0.05 ms/MB on one core)
-uint64_t hash_run(const unsigned char *b, size_t bytes, uint64_t salt) {
-  const size_t words = bytes / 8;
-  constexpr int L = 8;
-  uint64_t h[L] = {0x9E3779B97F4A7C15ull ^ salt, 0xC2B2AE3D27D4EB4Full, 0x165667B19E3779F9ull, 0x27D4EB2F165667C5ull,
-                   0x85EBCA77C2B2AE63ull, 0xD6E8FEB86659FD93ull, 0xA0761D6478BD642Full, 0xE7037ED1A0B428DBull};
-  size_t i = 0;
-  for (; i + L <= words; i += L) {
-    uint64_t w[L];
-    std::memcpy(w, b + 8 * i, 8 * L);
-    for (int k = 0; k < L; k++) { h[k] = (h[k] ^ w[k]) * 0x9FB21C651E98DF25ull; h[k] ^= h[k] >> 29; }
-  }
-  for (; i < words; i++) { uint64_t w; std::memcpy(&w, b + 8 * i, 8); h[i % L] = (h[i % L] ^ w) * 0x9FB21C651E98DF25ull; h[i % L] ^= h[i % L] >> 29; }
-  for (size_t t = 8 * words; t < bytes; t++) h[0] = (h[0] ^ b[t]) * 0x100000001B3ull;
-  uint64_t r = h[0];
-  for (int k = 1; k < L; k++) r = (r ^ h[k]) * 0xFF51AFD7ED558CCDull + k;
-  r ^= r >> 32;
-  return r;
-}
-
-// slice s of a buffer of `bytes` bytes: [lo, hi), split at multiples of 64 bytes (whole bs_value rows); the last slice
-// takes the remainder (a buffer below 1 KB is its last slice alone)
-inline void slice_range(size_t bytes, int s, size_t *lo, size_t *hi) {
-  const size_t part = (bytes / kSlices) & ~(size_t)63;
-  *lo = part * (size_t)s;
-  *hi = s == kSlices - 1 ? bytes : part * (size_t)(s + 1);
-}
-inline uint64_t combine_slices(const uint64_t *h) {
-  uint64_t r = h[0];
-  for (int p = 1; p < kSlices; p++) r = (r ^ h[p]) * 0xFF51AFD7ED558CCDull + p;
-  r ^= r >> 32;
-  return r ? r : 2;
-}
-
-// Slices [first, first + count) (mod kSlices) of up to four buffers as ONE pooled job: begin() hands the parts to the
-// workers and returns, end() takes what is left, waits, and leaves every requested slice's hash in out[buffer][slice].
-// Both are called inside one operator call.
-class SliceHasher {
- public:
-  struct Req { const void *data = nullptr; size_t bytes = 0; };
-  void begin(const Req *reqs, int n, int first, int count) {
-    parts_.clear();
-    for (int r = 0; r < n && r < 4; r++) {
-      const unsigned char *b = static_cast<const unsigned char *>(reqs[r].data);
-      if (!b) continue;
-      for (int c = 0; c < count && c < kSlices; c++) {
-        const int s = (first + c) % kSlices;
-        size_t lo, hi;
-        slice_range(reqs[r].bytes, s, &lo, &hi);
-        parts_.push_back({b + lo, hi - lo, (uint64_t)reqs[r].bytes + (uint64_t)s, &out[r][s]});
-      }
-    }
-    running_ = true;
-    HashPool::get().start((int)parts_.size(), [this](int k) {
-      const Part &pt = parts_[(size_t)k];
-      *pt.out = hash_run(pt.b, pt.bytes, pt.salt);
-    });
-  }
-  bool running() const { return running_; }
-  void end() {
-    if (!running_) return;
-    HashPool::get().finish();
-    running_ = false;
-  }
-  uint64_t out[4][kSlices] = {};
-
- private:
-  struct Part { const unsigned char *b; size_t bytes; uint64_t salt; uint64_t *out; };
-  std::vector<Part> parts_;
-  bool running_ = false;
-};
-
-// the whole content of one big buffer into its key (all slices, on the pool); begin / end so that the caller can do
-// something else in between (upload_reference hashes the points while they cross PCIe)
-struct FullHash {
-  SliceHasher sh;
-  void begin(const void *data, size_t bytes) { SliceHasher::Req r; r.data = data; r.bytes = bytes; sh.begin(&r, 1, 0, kSlices); }
-  void end(LegacyState::Key *k) {
-    sh.end();
-    std::memcpy(k->slice, sh.out[0], sizeof(k->slice));
-    k->full = combine_slices(k->slice);
-    k->full_known = true;
-  }
-};
-template <typename T>
-void full_hash_into(LegacyState::Key *k, const T *a, size_t n) {
-  if (!a) { std::memset(k->slice, 0, sizeof(k->slice)); k->full = 1; k->full_known = true; return; }
-  FullHash f;
-  f.begin(a, n * sizeof(T));
-  f.end(k);
-}
-// the small per-cell arrays: one run, on the caller
-template <typename T>
-uint64_t small_hash(const T *a, size_t n) {
-  if (!a) return 1;
-  const uint64_t r = hash_run(reinterpret_cast<const unsigned char *>(a), n * sizeof(T), n * sizeof(T));
-  return r ? r : 2;
-}
-
-// Does the caller's big buffer still hold what is resident?  Updates the key; `force`: recompute the hashes even if
-// address, length and the quick fingerprint are unchanged.  *hashed: the key's hashes were taken by this call.
-template <typename T>
-bool same_content(LegacyState::Key &k, const T *a, size_t n, bool force, bool *hashed) {
-  const uint64_t q = fingerprint(a, n);
-  const bool cheap_same = k.valid && k.addr == (const void *)a && k.n == n && k.quick == q;
-  if (cheap_same && !force) return true;
-  LegacyState::Key now;
-  full_hash_into(&now, a, n);
-  if (hashed) *hashed = true;
-  // a key whose hashes were never taken (trusted mode: CudaComputeHref's bs_value) is completed by its first full
-  // check; in the default mode a key without them counts as "changed"
-  bool same = k.valid && k.n == n && k.full_known && k.full == now.full;
-  if (cheap_same && !k.full_known && trust_buffers()) same = true;
-  now.addr = a; now.n = n; now.quick = q; now.valid = true;
-  k = now;
-  return same;
-}
-template <typename T>
-bool same_small(LegacyState::Key &k, const T *a, size_t n) {
-  const uint64_t f = small_hash(a, n);
-  const bool same = k.valid && k.addr == (const void *)a && k.n == n && k.full == f;
-  k.addr = a; k.n = n; k.quick = 0; k.full = f; k.valid = true; k.full_known = true;
-  return same;
-}
-template <typename T>
-void remember_small(LegacyState::Key &k, const T *a, size_t n) { (void)same_small(k, a, n); }
-template <typename T>
-void remember(LegacyState::Key &k, const T *a, size_t n) {
-  full_hash_into(&k, a, n);
-  k.addr = a; k.n = n; k.quick = fingerprint(a, n); k.valid = true;
-}
 
 bool to_u8(const double *im, size_t n, std::vector<uint8_t> *out);
 // An f64 image carrying u8 values (NID_pose_estimation.cpp:245-251), keyed like every big buffer on the caller's f64
 // bytes.  `have`: something is resident to compare with.  On return *same says whether the resident image can stay; u8
 // holds the converted image (the conversion checks every value: an integer in [0, 255] or the call fails) when it cannot.
-int check_image(LegacyState::Key &k, const double *im, size_t n, bool force, bool have, std::vector<uint8_t> *u8, bool *same,
+int check_image(Key &k, const double *im, size_t n, bool force, bool have, std::vector<uint8_t> *u8, bool *same,
                 bool *hashed) {
   u8->clear();
-  *same = same_content(k, im, n, force || !have, hashed) && have;
+  *same = same_content(k, im, n, force || !have, trust_buffers(), hashed) && have;
   if (*same) return NID_OK;
   if (!to_u8(im, n, u8)) { k.valid = false; return NID_ERR_UNSUPPORTED; }
   return NID_OK;
@@ -425,29 +169,24 @@ void report(const char *where, int rc, nid_multi *m) {
 // (18 of the pyramid's 33 ms per pair went there).  At most kParkedMax of them are kept; a parked context holds no
 // resident kernel and its caller-buffer keys are dropped.
 constexpr size_t kParkedMax = 4;
-std::vector<LegacyState> g_parked;
+struct Parked { nid_multi *m; PairShape shape; };
+std::vector<Parked> g_parked;
 
 void apply_options(nid_multi *m, int cell);
 
 nid_multi *get_multi(int rows, int cols, int cell, int bins, int deg, const double *intr) {
   LegacyState &S = g_state;
-  auto matches = [&](const LegacyState &T) {
-    return T.m && T.rows == rows && T.cols == cols && T.cell == cell && T.bins == bins &&
-           T.intr[0] == intr[0] && T.intr[1] == intr[1] && T.intr[2] == intr[2] && T.intr[3] == intr[3];
-  };
-  if (matches(S)) return S.m;
+  const PairShape want = {rows, cols, cell, bins, {intr[0], intr[1], intr[2], intr[3]}};
+  if (S.m && S.shape == want) return S.m;
   if (S.m) {  // park the current context
     (void)nid_multi_resident_pause(S.m);
-    LegacyState keep;
-    keep.m = S.m; keep.rows = S.rows; keep.cols = S.cols; keep.cell = S.cell; keep.bins = S.bins;
-    std::memcpy(keep.intr, S.intr, sizeof(keep.intr));
-    g_parked.push_back(keep);
+    g_parked.push_back({S.m, S.shape});
     if (g_parked.size() > kParkedMax) { nid_multi_destroy(g_parked.front().m); g_parked.erase(g_parked.begin()); }
   }
-  S = LegacyState();
+  S = LegacyState();  // (no keys, nothing "resident": the next call hands its pair over afresh)
   for (size_t k = 0; k < g_parked.size(); k++)
-    if (matches(g_parked[k])) {
-      S = g_parked[k];  // (no keys, nothing "resident": the next call hands its pair over afresh)
+    if (g_parked[k].shape == want) {
+      S.m = g_parked[k].m; S.shape = want;
       g_parked.erase(g_parked.begin() + (long)k);
       apply_options(S.m, cell);
       return S.m;
@@ -471,8 +210,7 @@ nid_multi *get_multi(int rows, int cols, int cell, int bins, int deg, const doub
     if (rc != NID_OK) { report("nid_multi_attach_comm", rc, m); nid_multi_destroy(m); return nullptr; }
   }
   apply_options(m, cell);
-  S.m = m; S.rows = rows; S.cols = cols; S.cell = cell; S.bins = bins;
-  std::memcpy(S.intr, intr, sizeof(S.intr));
+  S.m = m; S.shape = want;
   return m;
 }
 
@@ -494,7 +232,7 @@ bool to_u8(const double *im, size_t n, std::vector<uint8_t> *out) {
 
 // (`im`: im0 converted already, with its key up to date -- or empty: converted and keyed here)
 int upload_reference(LegacyState &S, const double *im0, const double *points3d, std::vector<uint8_t> *im, bool points_keyed) {
-  const size_t N = (size_t)S.rows * S.cols;
+  const size_t N = (size_t)S.shape.rows * S.shape.cols;
   std::vector<uint8_t> local;
   if (!im || im->empty()) {
     bool dummy;
@@ -507,9 +245,9 @@ int upload_reference(LegacyState &S, const double *im0, const double *points3d, 
   if (!points_keyed) fh.begin(points3d, 3 * N * sizeof(double));
   int rc = nid_multi_set_reference_points(S.m, points3d, im->data());
   if (!points_keyed) {
-    LegacyState::Key k;
+    Key k;
     fh.end(&k);  // (on every path: the pool is held until then)
-    k.addr = points3d; k.n = 3 * N; k.quick = fingerprint(points3d, 3 * N); k.valid = true;
+    k.stamp(points3d, 3 * N);
     if (rc == NID_OK) S.k_points = k;
   }
   if (rc != NID_OK) return rc;
@@ -520,14 +258,14 @@ int upload_reference(LegacyState &S, const double *im0, const double *points3d, 
 }
 
 int ensure_reference(LegacyState &S, const double *im0, const double *points3d, bool force) {
-  const size_t N = (size_t)S.rows * S.cols;
+  const size_t N = (size_t)S.shape.rows * S.shape.cols;
   std::vector<uint8_t> im;
   bool points_keyed = false;
   if (S.have_ref && !always_upload()) {
     bool a = false, hashed_a = false, hashed_b = false;
     int rc = check_image(S.k_im0, im0, N, force, true, &im, &a, &hashed_a);
     if (rc != NID_OK) return rc;
-    const bool b = same_content(S.k_points, points3d, 3 * N, force, &hashed_b);
+    const bool b = same_content(S.k_points, points3d, 3 * N, force, trust_buffers(), &hashed_b);
     points_keyed = true;
     if (hashed_a && hashed_b) S.fresh |= NID_LEGACY_REFERENCE;
     if (a && b) return NID_OK;
@@ -588,9 +326,7 @@ void CudaComputeHref(double *im0, double *points3d, double *pose, double *camera
   } else if (bs_value) {
     // trusted buffers: address, length and the sampled fingerprint now and NO full hash (0.25 ms even on the pool); the
     // first full check that reaches the key -- the kRehashEvery-th call of the pair, nid_legacy_invalidate -- takes it.
-    S.k_bs_ref = LegacyState::Key();
-    S.k_bs_ref.addr = bs_value; S.k_bs_ref.n = 4 * N; S.k_bs_ref.full = 0; S.k_bs_ref.full_known = false;
-    S.k_bs_ref.quick = fingerprint(bs_value, 4 * N); S.k_bs_ref.valid = true;
+    S.k_bs_ref = Key::cheap_only(bs_value, 4 * N);
   } else {
     remember(S.k_bs_ref, bs_value, 0);
   }
@@ -612,7 +348,7 @@ struct CallArgs {
 };
 nid_multi *ensure_state(const CallArgs &a);
 void verify_begin(const CallArgs &a, bool long_call);
-unsigned verify_end(const CallArgs &a);
+unsigned verify_end();
 nid_multi *follow_change(const CallArgs &a, unsigned stale);
 }
 
@@ -632,7 +368,7 @@ void CudaComputeH(bool calculate_der, double *im0, double *im1, double *points3d
   verify_begin(a, calculate_der);
   int rc = nid_multi_evaluate_matrix(m, pose, calculate_der ? 1 : 0, ht.data(), hj.data(), nullptr, calculate_der ? der : nullptr);
   // ... and the workers are joined here, on every path: no read of a caller buffer outlives the call
-  const unsigned stale = verify_end(a);
+  const unsigned stale = verify_end();
   if (rc != NID_OK) { report("CudaComputeH", rc, m); return; }
   if (stale) {
     // a buffer rewritten in place: what was just evaluated may be its old content -- upload what differs, evaluate again
@@ -693,7 +429,7 @@ nid_multi *ensure_state(const CallArgs &a) {
   bool same = S.have_href && !always_upload();
   bool keyed = false;  // bs_ref's slice hashes were taken by this call
   if (same) {
-    const bool x = same_content(S.k_bs_ref, a.bs_ref, 4 * N, fh, &keyed), y = same_small(S.k_counter, a.bs_counter, (size_t)ncell);
+    const bool x = same_content(S.k_bs_ref, a.bs_ref, 4 * N, fh, trust_buffers(), &keyed), y = same_small(S.k_counter, a.bs_counter, (size_t)ncell);
     const bool z = !a.Href || same_small(S.k_href, a.Href, (size_t)ncell);
     if (keyed) S.fresh |= NID_LEGACY_HREF_STATE;
     same = x && y && z;
@@ -705,7 +441,7 @@ nid_multi *ensure_state(const CallArgs &a) {
     if (rc != NID_OK) { report("CudaComputeH(href state upload)", rc, m); return nullptr; }
     if (!keyed) remember(S.k_bs_ref, a.bs_ref, 4 * N);
     remember_small(S.k_counter, a.bs_counter, (size_t)ncell);
-    if (a.Href) remember_small(S.k_href, a.Href, (size_t)ncell); else S.k_href = LegacyState::Key();
+    if (a.Href) remember_small(S.k_href, a.Href, (size_t)ncell); else S.k_href = Key();
     S.have_href = true;
     S.fresh |= NID_LEGACY_HREF_STATE;
     g_uploads++;
@@ -718,8 +454,15 @@ nid_multi *ensure_state(const CallArgs &a) {
 // bs_ref -- those whose keys this very call has not just taken -- go to the pool's workers (verify_begin, right before the
 // evaluation is launched); verify_end joins them and returns the parts (NID_LEGACY_*) whose slice no longer hashes to the
 // key's value.  Both inside the operator: the caller's buffers are not read once it has returned.
-SliceHasher g_verify;
-struct VerifyPlan { const LegacyState::Key *key[4]; const void *addr[4]; size_t n[4]; bool on[4]; int first, count; } g_plan;
+Verifier g_verifier;
+
+// the four big caller buffers of a call, each with the key of what is resident and the part it belongs to
+WatchTable watched_buffers(const LegacyState &S, const CallArgs &a) {
+  const size_t N = (size_t)a.rows * a.cols;
+  const size_t d = sizeof(double);
+  return {{{&S.k_im0, a.im0, N, d, NID_LEGACY_REFERENCE, "im0"}, {&S.k_points, a.points3d, 3 * N, d, NID_LEGACY_REFERENCE, "points3d"},
+           {&S.k_im1, a.im1, N, d, NID_LEGACY_TARGET, "im1"}, {&S.k_bs_ref, a.bs_ref, 4 * N, d, NID_LEGACY_HREF_STATE, "bs_ref"}}};
+}
 
 void verify_begin(const CallArgs &a, bool long_call) {
   LegacyState &S = g_state;
@@ -729,51 +472,21 @@ void verify_begin(const CallArgs &a, bool long_call) {
   // (20 against 10 us of device time at 640x480; the pool reads ~45 MB/ms), so it takes 1.5 k slices and a cost-only call
   // 0.75 k -- the LM's pattern of one in four covers 15/16 k per call on average (profiles/r06_legacy_call_cost.txt)
   if (k < kSlices && k >= 4) k = long_call ? k + k / 2 : k - k / 4;
-  const size_t N = (size_t)a.rows * a.cols;
-  static const unsigned part[4] = {NID_LEGACY_REFERENCE, NID_LEGACY_REFERENCE, NID_LEGACY_TARGET, NID_LEGACY_HREF_STATE};
-  const LegacyState::Key *key[4] = {&S.k_im0, &S.k_points, &S.k_im1, &S.k_bs_ref};
-  const void *addr[4] = {a.im0, a.points3d, a.im1, a.bs_ref};
-  const size_t cnt[4] = {N, 3 * N, N, 4 * N};
-  SliceHasher::Req req[4];
-  bool any = false;
-  for (int b = 0; b < 4; b++) {
-    g_plan.key[b] = key[b]; g_plan.addr[b] = addr[b]; g_plan.n[b] = cnt[b];
-    g_plan.on[b] = !(S.fresh & part[b]) && key[b]->valid && key[b]->full_known && key[b]->addr == addr[b] && key[b]->n == cnt[b] && addr[b];
-    req[b].data = g_plan.on[b] ? addr[b] : nullptr;
-    req[b].bytes = cnt[b] * sizeof(double);
-    any = any || g_plan.on[b];
-  }
-  if (!any) return;
-  g_plan.count = k;
-  g_plan.first = (int)(S.rot % kSlices);
-  S.rot += (unsigned long)k;
-  g_verify.begin(req, 4, g_plan.first, g_plan.count);
+  // (the cursor moves only when some buffer is verified: a call that has just keyed everything takes no turn)
+  if (g_verifier.begin(watched_buffers(S, a), S.fresh, (int)(S.rot % kSlices), k)) S.rot += (unsigned long)k;
 }
 
-unsigned verify_end(const CallArgs &a) {
-  (void)a;
-  if (!g_verify.running()) return 0;
-  g_verify.end();
-  static const unsigned part[4] = {NID_LEGACY_REFERENCE, NID_LEGACY_REFERENCE, NID_LEGACY_TARGET, NID_LEGACY_HREF_STATE};
-  static const char *what[4] = {"im0", "points3d", "im1", "bs_ref"};
-  unsigned stale = 0;
-  for (int b = 0; b < 4; b++) {
-    if (!g_plan.on[b]) continue;
-    for (int c = 0; c < g_plan.count; c++) {
-      const int s = (g_plan.first + c) % kSlices;
-      if (g_verify.out[b][s] == g_plan.key[b]->slice[s]) continue;
-      stale |= part[b];
-      if (g_plan.count < kSlices) {  // (every slice on every call: nothing stale was ever evaluated -- followed silently, like the reference)
-        std::fprintf(stderr, "[nid legacy] the caller's %s buffer was rewritten IN PLACE between two CudaComputeH calls (slice %d of %d no "
-                             "longer matches what is on the device): earlier calls may have evaluated its old content; uploading the new "
-                             "content and evaluating again.  nid_legacy_invalidate() announces such a change, "
-                             "nid_legacy_set_verify_mode(NID_LEGACY_VERIFY_EVERY_CALL) checks every slice on every call.\n", what[b], s, kSlices);
-        g_stale_detections++;
-      }
-      break;
-    }
+unsigned verify_end() {
+  const Verifier::Stale r = g_verifier.end();
+  // (every slice on every call: nothing stale was ever evaluated -- followed silently, like the reference)
+  for (int b = 0; b < r.n && r.count < kSlices; b++) {
+    std::fprintf(stderr, "[nid legacy] the caller's %s buffer was rewritten IN PLACE between two CudaComputeH calls (slice %d of %d no "
+                         "longer matches what is on the device): earlier calls may have evaluated its old content; uploading the new "
+                         "content and evaluating again.  nid_legacy_invalidate() announces such a change, "
+                         "nid_legacy_set_verify_mode(NID_LEGACY_VERIFY_EVERY_CALL) checks every slice on every call.\n", r.at[b].name, r.at[b].slice, kSlices);
+    g_stale_detections++;
   }
-  return stale;
+  return r.parts;
 }
 
 nid_multi *follow_change(const CallArgs &a, unsigned stale) {
@@ -803,7 +516,7 @@ void nid_legacy_set_resident(int on) {
 void nid_legacy_set_launch_shape(int jac_threads, int cost_threads) {
   g_jac_threads = jac_threads; g_cost_threads = cost_threads;
   if (g_state.m)
-    nid_multi_set_launch_shape(g_state.m, jac_threads_for(g_state.cell * g_state.cell, g_world > 1 ? g_world : (int)g_devices.size()),
+    nid_multi_set_launch_shape(g_state.m, jac_threads_for(g_state.shape.cell * g_state.shape.cell, g_world > 1 ? g_world : (int)g_devices.size()),
                                cost_threads);
 }
 
@@ -846,7 +559,7 @@ long nid_legacy_stale_detections(void) { return g_stale_detections; }
 
 void nid_legacy_reset(void) {
   if (g_state.m) nid_multi_destroy(g_state.m);
-  for (LegacyState &T : g_parked) nid_multi_destroy(T.m);
+  for (Parked &p : g_parked) nid_multi_destroy(p.m);
   g_parked.clear();
   g_state = LegacyState();
   (void)nid_backproject_release();  // Calculate3Dpoint's scratch
@@ -864,7 +577,7 @@ nid_multi *nid_legacy_prepare(double *im0, double *im1, double *points3d, int *b
   if (!m) return nullptr;
   // (no evaluation to overlap with: this call's slices are hashed on the spot)
   verify_begin(a, false);
-  const unsigned stale = verify_end(a);
+  const unsigned stale = verify_end();
   return stale ? follow_change(a, stale) : m;
 }
 
@@ -877,7 +590,7 @@ nid_multi *nid_legacy_set_pair_u16(const uint16_t *depth_u16, const uint8_t *im0
   nid_multi *m = get_multi(rows, cols, cell_num, bin_num, bs_degree, camera_intrincis);
   if (!m) return nullptr;
   LegacyState &S = g_state;
-  S.k_im0 = S.k_points = S.k_im1 = S.k_bs_ref = S.k_counter = S.k_href = LegacyState::Key();
+  S.k_im0 = S.k_points = S.k_im1 = S.k_bs_ref = S.k_counter = S.k_href = Key();
   S.have_ref = S.have_target = S.have_href = false;
   S.calls = 0;
   int rc = nid_multi_set_pair_u16(m, depth_u16, camera_intrincis[4], im0, im1, T_wc0_colmajor16, nullptr, pose0_colmajor16, bs_counter, Href);

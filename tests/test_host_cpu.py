@@ -181,6 +181,75 @@ def test_fork_between_legacy_calls_asan(tmp_path):
     assert r.returncode == 0 and "fork ok" in r.stdout and "AddressSanitizer" not in r.stderr, (r.returncode, r.stderr[-3000:])
 
 
+HOST_SRC = os.path.join(ROOT, "nid-pose-estimation_amd", "host")
+
+
+def _buffer_watch_check(tmp_path, name, flags):
+    """tests/cpp/buffer_watch_check.cpp + host/nid_buffer_watch.h and nothing else, built with `flags` (warnings are
+    errors) and run once per pool setting -- the pool reads its two environment variables once per process: 0, 1, 3 and 15
+    workers, polling for 150 us behind a job (the default) and parking at once (every job through park and wake).
+    Returns [(setting, CompletedProcess)]."""
+    exe = tmp_path / name
+    subprocess.check_call(["g++", *flags, "-g", "-std=c++17", "-pthread", "-Wall", "-Wextra", "-Werror", "-I", HOST_SRC,
+                           os.path.join(ROOT, "tests", "cpp", "buffer_watch_check.cpp"), "-o", str(exe)])
+    runs = []
+    for threads in ("0", "1", "3", "15"):
+        for spin in ("150", "0"):
+            env = dict(os.environ, NID_LEGACY_HASH_THREADS=threads, NID_LEGACY_HASH_SPIN_US=spin, ASAN_OPTIONS="detect_leaks=0", TSAN_OPTIONS="halt_on_error=0")
+            env.pop("LD_PRELOAD", None)
+            runs.append(((threads, spin), subprocess.run([str(exe)], capture_output=True, text=True, timeout=240, env=env)))
+    return runs
+
+
+def _assert_buffer_watch_runs(runs, fork):
+    for (threads, spin), r in runs:
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (threads, spin, r.stdout[-3000:], r.stderr[-4000:])
+        m = re.search(r"buffer watch \((\d+) workers, (\d+) us of polling\): (\d+) lengths sliced, (\d+) bits flipped, (\d+) pool jobs, fork ([a-zA-Z ]+), "
+                      r"(\d+) verifying calls, (\d+) checks, 0 failures\s*$", r.stdout)
+        assert m and (m.group(1), m.group(2)) == (threads, spin), r.stdout[-2000:]
+        assert int(m.group(3)) >= 26 and int(m.group(4)) >= 8 * 600 * 601 // 2 and int(m.group(5)) >= 3000 and int(m.group(7)) >= 10000, r.stdout
+        assert m.group(6) == fork, r.stdout
+
+
+def test_buffer_watch_alone_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+    """host/nid_buffer_watch.h (the legacy operators' watch over the caller's buffers: no HIP, no C-ABI) through
+    tests/cpp/buffer_watch_check.cpp, a stand-alone program: the 128 slices partition every length (awkward ones and the
+    operators' own) at multiples of 64 bytes, below 8 KB only the last is non-empty; every single bit of every length
+    1 .. 600 changes its slice's hash and the combined one, the salt counts, no digest is 0, three fixed inputs hash to
+    what the functions gave before they moved; the pool runs every part of 0 .. 512 exactly once, through thousands of
+    back-to-back jobs and after its workers have parked; fork() after a job leaves a child without workers that hashes
+    alone and a parent that goes on; the keys' rules (nothing hashed for an unchanged buffer, content at a new address,
+    the blind spot off the 64 samples, a key without hashes changed by default and completed on request); and a byte
+    changed in slice s of one of four buffers is reported with s by exactly the calls whose window holds s, for 1, 3, 6
+    and 128 slices per call from cursors that wrap -- not for a fresh part, another address, a key without hashes or no
+    buffer, and with nothing to verify no job is started."""
+    _assert_buffer_watch_runs(_buffer_watch_check(tmp_path, "buffer_watch_asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                                                                                 "-fno-omit-frame-pointer", "-O1"]), fork="ok")
+
+
+def test_buffer_watch_alone_under_thread_sanitizer(tmp_path):
+    """The same program under ThreadSanitizer, per pool setting: parts claimed on the job's own counter, workers woken
+    through the generation word, what they wrote read behind finish() -- no data race with 0 to 15 workers, polling or
+    parked.  (fork() is left to the other builds.)"""
+    runs = _buffer_watch_check(tmp_path, "buffer_watch_tsan", ["-fsanitize=thread", "-fno-omit-frame-pointer", "-O1"])
+    if any("unexpected memory mapping" in r.stderr for _, r in runs):
+        pytest.skip("ThreadSanitizer cannot map its shadow memory in this environment")
+    _assert_buffer_watch_runs(runs, fork="not run under ThreadSanitizer")
+
+
+def test_buffer_watch_alone_as_the_library_compiles_it(tmp_path):
+    """The same program with the host library's own flags (-O2 -ffp-contract=off, no sanitizer): the recorded digests hold
+    for the code as it ships.  And what keeps the header checkable alone: it includes no project header, names no
+    operator macro, mode or stderr; host/legacy_ops.cpp holds no thread, atomic or hash of its own."""
+    _assert_buffer_watch_runs(_buffer_watch_check(tmp_path, "buffer_watch_o2", ["-O2", "-ffp-contract=off", "-fPIC"]), fork="ok")
+    code = lambda path: "\n".join(line.split("//", 1)[0] for line in open(path).read().splitlines())
+    header, ops = code(os.path.join(HOST_SRC, "nid_buffer_watch.h")), code(os.path.join(HOST_SRC, "legacy_ops.cpp"))
+    assert not re.search(r'#include\s+"', header) and "stderr" not in header and "printf" not in header
+    assert set(re.findall(r"\b(?:NID|nid)_\w+", header)) == {"NID_LEGACY_HASH_THREADS", "NID_LEGACY_HASH_SPIN_US", "nid_watch"}
+    assert not re.search(r"pthread_|std::atomic|std::thread|std::mutex|<atomic>|<thread>|<mutex>|0x[0-9A-Fa-f]{16}", ops)
+    assert ops.count('#include "nid_buffer_watch.h"') == 1
+
+
 def test_pyramid_downsampling_matches_oracle(hostlib, oracle):
     """Own pyramid definition (host/nid_pyramid.cpp) against its numpy restatement: 2x2 box mean rounded half
     up for the images; valid-mean with 0 = invalid for the depth (holes, out-of-range values, mixed blocks)."""
