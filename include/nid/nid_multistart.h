@@ -23,6 +23,12 @@
  *   A chain that goes on solves and produces the next trial pose.  A FINISHED chain is frozen: its state, pose and
  *   record no longer change, whatever blocks it is handed -- the result does not depend on how many rounds are
  *   enqueued past its end, or on the chunks the host enqueues them in.
+ * What "restates" covers: the rule, branch for branch, and the idea of the host stack's 6x6 solver (LinearSolverDense:
+ * the largest remaining |diagonal| next, positive or fail) -- not its elimination order.  Where lambda is below the
+ * rounding of H (lambda < 2^-40 max|H_jj|; seen only at <= 5.3e-16 of it, on singular H) the damped matrix is singular
+ * to rounding and the two solvers can decide differently on success, or on x; everywhere else they agree on success and
+ * on x to 1e-9 relative, and the chains give the shipped LM's trials per outer iteration
+ * (tests/cpp/lm_step_flows_check.cpp over the recorded trace tests/golden/lm_flows_trace.json).
  *
  * Out of scope: cell shards over several GPUs (nid_multi.h contexts: use one context that owns all cells), more
  * than NID_MAX_BATCH = 256 chains per call, and compacting finished chains out of the grid (a finished chain's
@@ -100,6 +106,14 @@ typedef struct {
  * (state->rec_q; the start pose's for a fresh chain).  Returns 1 while the chain is running, 0 once it is finished,
  * NID_ERR_INVALID_ARG for a null pointer. */
 int nid_lm_step_host(nid_ms_state *state, const double *reduced32);
+
+/* One launch of k_lm_step (the kernel nid_multistart_lm's rounds run) over n caller-given chains: tests, debugging.
+ * states[n] in/out; reduced32: n x 32; rec19 (n x 19: q[7], M[12]) and rec_mode[n] in/out -- uploaded into the records
+ * first, so a record the kernel does not write comes back as passed in; trace[n] (may be NULL); *running: the word.
+ * Buffers are the call's own (the multi-start pool is not touched); no pair need be set.  NID_ERR_INVALID_ARG for a
+ * null pointer (but trace) or unless 1 <= n <= 65536; NID_ERR_STATE while a launch is pending. */
+int nid_lm_step_device(nid_ctx *ctx, nid_ms_state *states, const double *reduced32, int n, double *rec19,
+                       int32_t *rec_mode, nid_ms_trace *trace, unsigned *running);
 
 /* n_chains Levenberg-Marquardt chains from poses7_in (n_chains x 7) on the context's frame pair, at most
  * `iterations` outer iterations each.  A round is one grid of n_chains poses with the Jacobian in the context's

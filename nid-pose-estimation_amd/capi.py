@@ -50,7 +50,7 @@ SYMBOLS = [
 ]
 
 # include/nid/nid_multistart.h (a header of its own: the symbols above are nid_c.h's, pinned by tests/test_abi.py)
-MULTISTART_SYMBOLS = ["nid_multistart_lm", "nid_lm_step_host"]
+MULTISTART_SYMBOLS = ["nid_multistart_lm", "nid_lm_step_host", "nid_lm_step_device"]
 MS_RUNNING, MS_ITERATIONS, MS_TRIALS_EXHAUSTED, MS_RHO_NOT_NEGATIVE, MS_NBAD = 0, 1, 2, 3, 4
 MS_F_FIRST, MS_F_ACCEPT, MS_F_REJECT, MS_F_OUTER_END, MS_F_SOLVE_FAILED, MS_F_FINISHED = 1, 2, 4, 8, 16, 32
 
@@ -217,6 +217,8 @@ def load():
     if hasattr(lib, "nid_multistart_lm"):   # (an older experiment build, NID_HIP_LIB, lacks it: calling it is an error there)
         lib.nid_multistart_lm.argtypes = [vp, c_dp, C.c_int, C.c_int, C.c_double, C.c_int, vp, c_ip, vp, c_ip]
         lib.nid_lm_step_host.argtypes = [C.POINTER(MsState), c_dp]
+    if hasattr(lib, "nid_lm_step_device"):   # (likewise)
+        lib.nid_lm_step_device.argtypes = [vp, C.POINTER(MsState), c_dp, C.c_int, c_dp, c_ip, vp, C.POINTER(C.c_uint32)]
     if hasattr(lib, "nid_pyr_create"):   # (an older experiment build, NID_HIP_LIB, lacks it: calling it is an error there)
         u16p = C.POINTER(C.c_uint16)
         lib.nid_pyr_level_config.argtypes = [C.POINTER(NidConfig), C.c_int, C.POINTER(NidConfig)]
@@ -640,6 +642,21 @@ def lm_step_host(state, reduced32):
     if rc < 0:
         raise NidError(f"nid_lm_step_host: {rc}")
     return bool(rc)
+
+
+def lm_step_device(states, reduced32, ctx, rec19, rec_mode, trace=True):
+    """One launch of k_lm_step over caller-given chains on ctx (nid_lm_step_device).  states: a ctypes array of MsState, stepped
+    in place; reduced32 [n, 32]; rec19 [n, 19] float64 and rec_mode [n] int32: the pose records as handed to the kernel,
+    replaced by what it left.  Returns (running word, trace): trace an MS_TRACE_DTYPE array [n], or None."""
+    n = len(states)
+    r = _d(reduced32)
+    assert r.size == n * NID_REDUCED_LEN and rec19.dtype == np.float64 and rec19.size == n * 19 and rec19.flags.c_contiguous
+    assert rec_mode.dtype == np.int32 and rec_mode.size == n and rec_mode.flags.c_contiguous
+    tr = np.zeros(max(n, 1), dtype=MS_TRACE_DTYPE) if trace else None
+    word = C.c_uint32(0)
+    ctx._check(ctx.lib.nid_lm_step_device(ctx.h, states, _dp(r), n, _dp(rec19), _ip(rec_mode),
+                                          tr.ctypes.data_as(C.c_void_p) if trace else None, C.byref(word)), "nid_lm_step_device")
+    return int(word.value), (tr[:n] if trace else None)
 
 
 def log2_fast_host(x):

@@ -100,6 +100,62 @@ int nid_lm_step_host(nid_ms_state *state, const double *reduced32) {
   return lm::lm_step(state, reduced32) ? 1 : 0;
 }
 
+// k_lm_step alone on what the caller brings: buffers of the call's own (the context's multi-start pool is not touched),
+// the records uploaded first so that one the kernel leaves alone comes back as it went in
+int nid_lm_step_device(nid_ctx *ctx, nid_ms_state *states, const double *reduced32, int n, double *rec19, int32_t *rec_mode,
+                       nid_ms_trace *trace, unsigned *running) {
+  if (!ctx || !states || !reduced32 || !rec19 || !rec_mode || !running || n < 1 || n > (1 << 16)) return NID_ERR_INVALID_ARG;
+  if (any_pending(ctx)) { ctx->last_error = "a launch is pending: nid_wait() it first"; return NID_ERR_STATE; }
+  NID_HIP(ctx, hipSetDevice(ctx->cfg.device));
+  resident_retire(ctx);  // (the buffers below are allocated and released here: a release waits for the whole device)
+  const size_t m = (size_t)n;
+  DevBuf<nid_ms_state> state_dev;
+  DevBuf<SlotArgs> recs_dev;
+  DevBuf<double> reduced_dev;
+  DevBuf<nid_ms_trace> trace_dev;
+  DevBuf<unsigned> running_dev;
+  NID_HIP(ctx, state_dev.alloc(m));
+  NID_HIP(ctx, recs_dev.alloc(m));
+  NID_HIP(ctx, reduced_dev.alloc(m * kReducedLen));
+  NID_HIP(ctx, running_dev.alloc(1));
+  if (trace) NID_HIP(ctx, trace_dev.alloc(m));
+  std::vector<SlotArgs> recs(m);  // (value-initialised: only the `pose` member means anything here)
+  for (size_t k = 0; k < m; k++) {
+    Pose &P = recs[k].pose;
+    for (int i = 0; i < 7; i++) P.q[i] = rec19[19 * k + i];
+    for (int i = 0; i < 12; i++) P.M[i] = rec19[19 * k + 7 + i];
+    P.mode = rec_mode[k];
+  }
+  hipStream_t st = ctx->stream;
+  auto drain = [&]() { (void)hipStreamSynchronize(st); };  // (the buffers go when this call returns: nothing may still use them)
+  hipError_t e = hipMemcpyAsync(state_dev, states, m * sizeof(nid_ms_state), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(recs_dev, recs.data(), m * sizeof(SlotArgs), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(reduced_dev, reduced32, m * kReducedLen * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(running_dev, 0, sizeof(unsigned), st);
+  if (e == hipSuccess) {
+    MsStepArgs A{state_dev, recs_dev, reduced_dev, trace ? trace_dev.get() : nullptr, running_dev, n};
+    hipLaunchKernelGGL(k_lm_step, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, A);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(states, state_dev, m * sizeof(nid_ms_state), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(recs.data(), recs_dev, m * sizeof(SlotArgs), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && trace) e = hipMemcpyAsync(trace, trace_dev, m * sizeof(nid_ms_trace), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(running, running_dev, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+  if (e != hipSuccess) {
+    drain();
+    ctx->last_error = std::string("nid_lm_step_device: ") + hipGetErrorString(e);
+    return NID_ERR_HIP;
+  }
+  NID_HIP(ctx, hipStreamSynchronize(st));
+  for (size_t k = 0; k < m; k++) {
+    const Pose &P = recs[k].pose;
+    for (int i = 0; i < 7; i++) rec19[19 * k + i] = P.q[i];
+    for (int i = 0; i < 12; i++) rec19[19 * k + 7 + i] = P.M[i];
+    rec_mode[k] = P.mode;
+  }
+  return NID_OK;
+}
+
 int nid_multistart_lm(nid_ctx *ctx, const double *poses7_in, int n, int iterations, double delta, int max_rounds,
                       nid_ms_result *results, int *best, nid_ms_trace *trace, int *rounds_done) {
   if (!ctx || !poses7_in || !results || n < 1 || n > kMaxBatchExt || iterations < 1 || max_rounds < 0) return NID_ERR_INVALID_ARG;
