@@ -58,8 +58,9 @@
  * (min_consistent > 0).  And where the keyframe has no depth there is nothing to check a frame against: a moving object
  * seen through a hole cannot be told from the scene, and its depth is filled in like any other.
  *
- * Out of scope: refining depths that are already valid, fills on the target, cell shards, several devices, a fill plane on
- * the coarser levels.
+ * Refining depths that are already valid is nid_reffuse.h's; once a pyramid has been fused there, "uploaded" in THE RULE
+ * above reads as its BASE plane, fused ? fused : uploaded.  Out of scope: fills on the target, cell shards, several devices,
+ * a fill plane on the coarser levels.
  */
 #ifndef NID_REFFILL_H
 #define NID_REFFILL_H

@@ -131,6 +131,14 @@ REFFILL_COUNTS_DTYPE = np.dtype([("n_target_valid", "i8"), ("n_splat", "i8"), ("
                                  ("n_new", "i8"), ("n_filled", "i8"), ("reserved", "i8")])
 assert REFFILL_COUNTS_DTYPE.itemsize == 64
 
+# include/nid/nid_reffuse.h (likewise: the reference's valid depth refined from tracked frames, the tracker's use of it)
+REFFUSE_SYMBOLS = ["nid_pyr_fuse_reference_depth", "nid_pyr_clear_reference_fusion", "nid_pyr_get_reference_fused_u16",
+                   "nid_pyr_get_reference_fusion_obs_u8", "nid_reffuse_host", "nid_track_set_fusing", "nid_track_last_fusion"]
+REFFUSE_MAX_OBS = 255
+REFFUSE_COUNTS_DTYPE = np.dtype([("n_target_valid", "i8"), ("n_splat", "i8"), ("n_hit", "i8"), ("n_valid", "i8"), ("n_fused", "i8"),
+                                 ("n_gated", "i8"), ("n_saturated", "i8"), ("n_changed", "i8")])
+assert REFFUSE_COUNTS_DTYPE.itemsize == 64
+
 _lib = None
 
 
@@ -275,6 +283,16 @@ def load():
                                          C.c_int, u16p, vp]
         lib.nid_track_set_filling.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.nid_track_last_fill.argtypes = [vp, vp]
+    if hasattr(lib, "nid_pyr_fuse_reference_depth"):   # (likewise)
+        u16p = C.POINTER(C.c_uint16)
+        lib.nid_pyr_fuse_reference_depth.argtypes = [vp, c_dp, C.c_int, C.c_int, C.c_int, vp]
+        lib.nid_pyr_clear_reference_fusion.argtypes = [vp]
+        lib.nid_pyr_get_reference_fused_u16.argtypes = [vp, u16p]
+        lib.nid_pyr_get_reference_fusion_obs_u8.argtypes = [vp, c_u8p]
+        lib.nid_reffuse_host.argtypes = [C.POINTER(NidConfig), u16p, C.c_double, c_dp, u16p, C.c_double, c_dp, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(C.c_uint32), c_u8p, u16p, vp]
+        lib.nid_track_set_fusing.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        lib.nid_track_last_fusion.argtypes = [vp, vp]
     _lib = lib
     return lib
 
@@ -849,6 +867,30 @@ class Pyramid:
         self._check(self.lib.nid_pyr_get_reference_fill_u16(self.h, f.ctypes.data_as(C.POINTER(C.c_uint16))), "nid_pyr_get_reference_fill_u16")
         return f
 
+    def fuse_reference_depth(self, pose7, gate_abs=50, gate_rel_1024=20, max_obs=255):
+        """nid_pyr_fuse_reference_depth (nid_reffuse.h): the counts as a REFFUSE_COUNTS_DTYPE record."""
+        q = _d(pose7)
+        assert q.size == 7
+        n = np.zeros(1, dtype=REFFUSE_COUNTS_DTYPE)
+        self._check(self.lib.nid_pyr_fuse_reference_depth(self.h, _dp(q), int(gate_abs), int(gate_rel_1024), int(max_obs),
+                                                          n.ctypes.data_as(C.c_void_p)), "nid_pyr_fuse_reference_depth")
+        return n[0]
+
+    def clear_reference_fusion(self):
+        self._check(self.lib.nid_pyr_clear_reference_fusion(self.h), "nid_pyr_clear_reference_fusion")
+
+    def get_reference_fused(self):
+        """nid_pyr_get_reference_fused_u16: the FUSED plane (rows x cols of level 0) as the device holds it."""
+        f = np.zeros((self.cfg0.rows, self.cfg0.cols), dtype=np.uint16)
+        self._check(self.lib.nid_pyr_get_reference_fused_u16(self.h, f.ctypes.data_as(C.POINTER(C.c_uint16))), "nid_pyr_get_reference_fused_u16")
+        return f
+
+    def get_reference_fusion_obs(self):
+        """nid_pyr_get_reference_fusion_obs_u8: the OBS plane likewise."""
+        k = np.zeros((self.cfg0.rows, self.cfg0.cols), dtype=np.uint8)
+        self._check(self.lib.nid_pyr_get_reference_fusion_obs_u8(self.h, k.ctypes.data_as(c_u8p)), "nid_pyr_get_reference_fusion_obs_u8")
+        return k
+
     def get_level_inputs(self, level):
         """(depth_u16, im0, im1) of a level as the device holds them."""
         c = self.level_config(level)
@@ -1015,6 +1057,16 @@ class Tracker:
         self._check(self.lib.nid_track_last_fill(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_fill")
         return n[0]
 
+    def set_fusing(self, on, gate_abs=50, gate_rel_1024=20, max_obs=255):
+        """nid_track_set_fusing (nid_reffuse.h): off by default"""
+        self._check(self.lib.nid_track_set_fusing(self.h, int(on), int(gate_abs), int(gate_rel_1024), int(max_obs)), "nid_track_set_fusing")
+
+    def last_fusion(self):
+        """nid_track_last_fusion: the counts of the last push's fusion as a REFFUSE_COUNTS_DTYPE record (zeros: it ran none)"""
+        n = np.zeros(1, dtype=REFFUSE_COUNTS_DTYPE)
+        self._check(self.lib.nid_track_last_fusion(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_fusion")
+        return n[0]
+
     def push(self, im, depth_u16=None, depth_factor=1.0 / 5000, T_wc_first=None):
         """nid_track_push_u16: one frame.  Returns a dict of nid_track_result's members (pose7 and rounds as arrays)."""
         N = self.cfg0.rows * self.cfg0.cols
@@ -1099,6 +1151,31 @@ def reffill_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1,
     if rc != NID_OK:
         raise NidError(f"nid_reffill_host: {lib.nid_status_string(rc).decode()} ({rc})")
     return f.reshape(cfg.rows, cfg.cols), n[0]
+
+
+def reffuse_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1, pose7, gate_abs=50, gate_rel_1024=20, max_obs=255,
+                 sums=None, obs=None):
+    """nid_reffuse_host (nid_reffuse.h): one call of the rule on copies of `sums` and `obs` (None: zeros): (SUM plane
+    [rows, cols] u32, OBS plane u8, FUSED plane u16, counts as a REFFUSE_COUNTS_DTYPE record) -- what
+    nid_pyr_fuse_reference_depth computes, from the same text compiled for the host."""
+    lib = load()
+    N = cfg.rows * cfg.cols
+    u16p = C.POINTER(C.c_uint16)
+    d0 = np.ascontiguousarray(depth0_u16, dtype=np.uint16).reshape(-1)
+    d1 = np.ascontiguousarray(depth1_u16, dtype=np.uint16).reshape(-1)
+    T, q = _d(T_wc_colmajor16), _d(pose7)
+    s = np.zeros(N, dtype=np.uint32) if sums is None else np.array(sums, dtype=np.uint32).reshape(-1)
+    k = np.zeros(N, dtype=np.uint8) if obs is None else np.array(obs, dtype=np.uint8).reshape(-1)
+    f = np.zeros(N, dtype=np.uint16)
+    assert d0.size == N and d1.size == N and s.size == N and k.size == N and T.size == 16 and q.size == 7
+    n = np.zeros(1, dtype=REFFUSE_COUNTS_DTYPE)
+    rc = lib.nid_reffuse_host(C.byref(cfg), d0.ctypes.data_as(u16p), float(factor0), _dp(T), d1.ctypes.data_as(u16p), float(factor1), _dp(q),
+                              int(gate_abs), int(gate_rel_1024), int(max_obs), s.ctypes.data_as(C.POINTER(C.c_uint32)), k.ctypes.data_as(c_u8p),
+                              f.ctypes.data_as(u16p), n.ctypes.data_as(C.c_void_p))
+    if rc != NID_OK:
+        raise NidError(f"nid_reffuse_host: {lib.nid_status_string(rc).decode()} ({rc})")
+    shape = (cfg.rows, cfg.cols)
+    return s.reshape(shape), k.reshape(shape), f.reshape(shape), n[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -2161,3 +2161,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- depth for the reference's holes from tracked frames and the tracker's use of it (include/nid/nid_reffill.h) -----
 #include "nid_reffill.inc"
+
+// ---- the reference's valid depth refined from tracked frames and the tracker's use of it (include/nid/nid_reffuse.h) ---
+#include "nid_reffuse.inc"

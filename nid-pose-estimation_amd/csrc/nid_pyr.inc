@@ -49,8 +49,21 @@ struct nid_pyr {
       DevBuf<unsigned long long> counts_dev;    // [8]: nid_reffill_counts
       PinnedBuf<unsigned long long> counts_host;
     } fill;
-    // a new reference starts unmasked and unfilled
-    void new_reference(double factor) { ref_factor = factor; have_pristine = any_masked = fill.have_uploaded = fill.any_filled = false; }
+    // nid_reffuse.inc: the fusion's state and buffers -- made by the first fusion behind a new reference (have_state, which
+    // implies fill.have_uploaded), never by a caller who does not fuse.  With have_state, base_dev holds fused ? fused :
+    // uploaded, pristine_dev fill ? fill : base, and the fill reads base_dev where it read uploaded_dev
+    struct Fuse {
+      bool have_state = false;  // sum_dev / obs_dev / fused_dev / base_dev belong to the resident reference
+      bool any_fused = false;   // an entry of obs_dev is non-zero
+      DevBuf<uint32_t> sum_dev;             // S
+      DevBuf<uint8_t> obs_dev;              // k
+      DevBuf<uint16_t> fused_dev, base_dev;
+    } fuse;
+    // a new reference starts unmasked, unfilled and unfused
+    void new_reference(double factor) {
+      ref_factor = factor;
+      have_pristine = any_masked = fill.have_uploaded = fill.any_filled = fuse.have_state = fuse.any_fused = false;
+    }
   } rm;
 };
 

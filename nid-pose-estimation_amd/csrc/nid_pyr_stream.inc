@@ -33,6 +33,11 @@ struct nid_track {
   bool fill_on = false;
   int32_t fill_guard = 0, fill_guard_abs = 0, fill_guard_rel_1024 = 0;
   nid_reffill_counts last_fill = {}, push_fill = {};  // (push_fill: as push_mask)
+  // nid_reffuse.h (nid_reffuse.inc): whether such a frame refines the keyframe's valid depth, the gate, the cap, and the
+  // counts of the last push's fusion
+  bool fuse_on = false;
+  int32_t fuse_gate_abs = 0, fuse_gate_rel_1024 = 0, fuse_max_obs = 1;
+  nid_reffuse_counts last_fusion = {}, push_fusion = {};  // (push_fusion: as push_mask)
 };
 
 namespace {
@@ -190,6 +195,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   int32_t n_checked = 0;
   t->push_mask = nid_refmask_counts();  // (nid_refmask.h: step 5e's counts, if this push runs it)
   t->push_fill = nid_reffill_counts();  // (nid_reffill.h: the fill's counts, likewise)
+  t->push_fusion = nid_reffuse_counts();  // (nid_reffuse.h: the fusion's)
   int rc = nid_pyr_set_target_u8(p, im);
   if (rc) return rc;
   if (first) {
@@ -254,6 +260,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   t->n_checked = n_checked;
   t->last_mask = t->push_mask;
   t->last_fill = t->push_fill;
+  t->last_fusion = t->push_fusion;
   t->frame++;
   *out = R;
   return NID_OK;

@@ -6,6 +6,7 @@
 // zero fill plane if this is the first fill behind a new reference, and the fill's counts zeroed.  The call's own part:
 // the z-buffer's 0xFF bytes, k_reffill_splat and k_reffill_apply (the fill plane, pristine = fill ? fill : uploaded, the
 // counts) -- or, for nid_pyr_clear_reference_fill, zeros into the plane and the uploaded copy back into the pristine depth.
+// (Behind a fusion of nid_reffuse.h, "uploaded" in both is its BASE plane: rf_base.)
 // rf_finish: the counts' way home, the mask plane as it is into work_dev -- a final plane through dc::mask_final with
 // dilate 0 is itself --, and rm_finish, which makes the effective reference of it and closes the call with its one
 // synchronisation.  No evaluation kernel is launched, no SlotArgs filled, no slot touched.
@@ -26,9 +27,10 @@ int rf_ensure(nid_pyr *p) {
   return NID_OK;
 }
 
-// a fill call that fails behind rf_ensure: the planes may be half made (the reference is not ready either)
+// a fill call that fails behind rf_ensure: the planes may be half made (the reference is not ready either); the fusion's
+// state (nid_reffuse.inc) stands on them
 int rf_failed(nid_pyr *p, int rc) {
-  p->rm.fill.have_uploaded = p->rm.fill.any_filled = false;
+  p->rm.fill.have_uploaded = p->rm.fill.any_filled = p->rm.fuse.have_state = p->rm.fuse.any_fused = false;
   return rc;
 }
 
@@ -51,7 +53,36 @@ int rf_begin(nid_pyr *p, const char *what) {
   return NID_OK;
 }
 
-int rf_finish(nid_pyr *p, const char *what, nid_reffill_counts *out) {
+// part A's arguments for pose7 against the resident target depth (on the host: nothing is enqueued)
+RefFillArgs rf_splat_args(nid_pyr *p, const double *pose7) {
+  nid_ctx *c0 = p->ctx[0];
+  RefFillArgs A = {};
+  double Twc[16];  // the host's copy of the keyframe's matrix: where whatever made the reference staged it
+  std::memcpy(Twc, c0->pair_stage + pair_stage_layout(c0->g).twc, sizeof(Twc));
+  rf::target_to_keyframe(Twc, pose7, A.M);
+  A.d1 = p->tdepth_dev;
+  A.factor1 = p->tdepth_factor;
+  A.factor0 = p->rm.ref_factor;
+  return A;
+}
+
+// part A behind rf_begin: the z-buffer's 0xFF bytes and k_reffill_splat (words 0 and 1 of the call's totals)
+int rf_splat(nid_pyr *p, const char *what, const RefFillArgs &A) {
+  nid_pyr::RefMask::Fill &F = p->rm.fill;
+  const hipStream_t st = p->ctx[0]->stream;
+  const Geometry &g = p->ctx[0]->g;
+  const size_t N = (size_t)g.rows * g.cols;
+  if (hipMemsetAsync(F.zbuf_dev, 0xFF, 4 * N, st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(zbuf)");
+  hipLaunchKernelGGL(k_reffill_splat, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g, A, F.zbuf_dev.get(), F.counts_dev.get());
+  return NID_OK;
+}
+
+// the keyframe's own samples as a fill reads them: the BASE plane of nid_reffuse.h once a fusion state exists, else the
+// uploaded copy
+const uint16_t *rf_base(nid_pyr *p) { return p->rm.fuse.have_state ? p->rm.fuse.base_dev.get() : p->rm.fill.uploaded_dev.get(); }
+
+// the close of a fill call and of a fusion call (nid_reffuse.inc): behind it counts_host holds the call's eight totals
+int rf_close(nid_pyr *p, const char *what) {
   nid_pyr::RefMask &R = p->rm;
   nid_pyr::RefMask::Fill &F = R.fill;
   const hipStream_t st = p->ctx[0]->stream;
@@ -60,10 +91,17 @@ int rf_finish(nid_pyr *p, const char *what, nid_reffill_counts *out) {
   if (hipMemcpyAsync(R.work_dev, R.mask_dev, N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(work)");
   const int rc = rm_finish(p, what, 0, nullptr);
   if (rc) return rf_failed(p, rc);
+  F.have_uploaded = true;
+  return NID_OK;
+}
+
+int rf_finish(nid_pyr *p, const char *what, nid_reffill_counts *out) {
+  nid_pyr::RefMask::Fill &F = p->rm.fill;
+  const int rc = rf_close(p, what);
+  if (rc) return rc;
   static_assert(sizeof(nid_reffill_counts) == 8 * sizeof(unsigned long long), "the totals are the record");
   nid_reffill_counts n;
   std::memcpy(&n, F.counts_host.host(), sizeof(n));
-  F.have_uploaded = true;
   F.any_filled = n.n_filled != 0;
   if (out) *out = n;
   return NID_OK;
@@ -80,24 +118,15 @@ int nid_pyr_fill_reference_depth(nid_pyr *p, const double *pose7, int guard, int
   int rc = rm_refuse(p, what);
   if (rc) return rc;
   if (!p->have_tdepth) return pyr_fail(p, NID_ERR_STATE, "nid_pyr_fill_reference_depth: the target has no depth: nid_pyr_set_target_depth_u16() first");
-  nid_ctx *c0 = p->ctx[0];
   nid_pyr::RefMask &R = p->rm;
   nid_pyr::RefMask::Fill &F = R.fill;
-  RefFillArgs A = {};
-  double Twc[16];  // the host's copy of the keyframe's matrix: where whatever made the reference staged it
-  std::memcpy(Twc, c0->pair_stage + pair_stage_layout(c0->g).twc, sizeof(Twc));
-  rf::target_to_keyframe(Twc, pose7, A.M);
-  A.d1 = p->tdepth_dev;
-  A.factor1 = p->tdepth_factor;
-  A.factor0 = R.ref_factor;
+  const RefFillArgs A = rf_splat_args(p, pose7);
   if ((rc = rf_begin(p, what))) return rc;
-  const hipStream_t st = c0->stream;
-  const Geometry &g = c0->g;
-  const size_t N = (size_t)g.rows * g.cols;
-  if (hipMemsetAsync(F.zbuf_dev, 0xFF, 4 * N, st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(zbuf)");
-  hipLaunchKernelGGL(k_reffill_splat, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, g, A, F.zbuf_dev.get(), F.counts_dev.get());
+  if ((rc = rf_splat(p, what, A))) return rc;
+  const hipStream_t st = p->ctx[0]->stream;
+  const Geometry &g = p->ctx[0]->g;
   hipLaunchKernelGGL(k_reffill_apply, dim3((unsigned)((g.cols + kRmTileW - 1) / kRmTileW), (unsigned)((g.rows + kRmTileH - 1) / kRmTileH)), dim3(256),
-                     0, st, g.rows, g.cols, guard, guard_abs, guard_rel_1024, (int)(accumulate != 0), F.zbuf_dev.get(), F.uploaded_dev.get(),
+                     0, st, g.rows, g.cols, guard, guard_abs, guard_rel_1024, (int)(accumulate != 0), F.zbuf_dev.get(), rf_base(p),
                      R.ref_factor, F.fill_dev.get(), R.pristine_dev.get(), F.counts_dev.get());
   return rf_finish(p, what, out);
 }
@@ -114,7 +143,7 @@ int nid_pyr_clear_reference_fill(nid_pyr *p) {
   const hipStream_t st = p->ctx[0]->stream;
   const size_t N = (size_t)p->ctx[0]->g.rows * p->ctx[0]->g.cols;
   if (hipMemsetAsync(F.fill_dev, 0, 2 * N, st) != hipSuccess) return rf_failed(p, what, "hipMemsetAsync(fill)");
-  if (hipMemcpyAsync(R.pristine_dev, F.uploaded_dev, 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(pristine)");
+  if (hipMemcpyAsync(R.pristine_dev, rf_base(p), 2 * N, hipMemcpyDeviceToDevice, st) != hipSuccess) return rf_failed(p, what, "hipMemcpyAsync(pristine)");
   return rf_finish(p, what, nullptr);
 }
 

@@ -116,24 +116,34 @@ NID_DC_HD bool args_ok(int guard, int guard_abs, int guard_rel_1024) {
   return guard >= 0 && guard <= NID_REFFILL_MAX_GUARD && guard_abs >= 0 && guard_abs <= 65535 && guard_rel_1024 >= 0 && guard_rel_1024 <= 1024;
 }
 
-// nid_reffill_host behind its argument checks: THE RULE over the whole plane, in place.  d0: the keyframe's uploaded depth;
-// zbuf: rows x cols words of the caller's, overwritten.
-inline void reffill_host(const Splat &S, const uint16_t *d0, int guard, int guard_abs, int guard_rel_1024, int accumulate, uint16_t *fill,
-                         uint32_t *zbuf, nid_reffill_counts *counts) {
+// Part A over the whole target on the host (the fill's and, in nid_reffuse_rule.h, the fusion's): zbuf, rows x cols words of
+// the caller's, overwritten; the part's two counts
+inline void splat_host(const Splat &S, uint32_t *zbuf, int64_t *n_target_valid, int64_t *n_splat) {
   const int rows = S.rows, cols = S.cols;
   const size_t N = (size_t)rows * (size_t)cols;
-  nid_reffill_counts n = {};
+  int64_t valid = 0, splats = 0;
   for (size_t i = 0; i < N; i++) zbuf[i] = kNone;
   for (int r1 = 0; r1 < rows; r1++)
     for (int c1 = 0; c1 < cols; c1++) {
       size_t idx = 0;
       uint32_t q = 0;
       const int k = splat(S, r1, c1, &idx, &q);
-      n.n_target_valid += k >= 1;
+      valid += k >= 1;
       if (k != 2) continue;
-      n.n_splat++;
+      splats++;
       if (q < zbuf[idx]) zbuf[idx] = q;  // 6.
     }
+  *n_target_valid = valid;
+  *n_splat = splats;
+}
+
+// nid_reffill_host behind its argument checks: THE RULE over the whole plane, in place.  d0: the keyframe's uploaded depth;
+// zbuf: rows x cols words of the caller's, overwritten.
+inline void reffill_host(const Splat &S, const uint16_t *d0, int guard, int guard_abs, int guard_rel_1024, int accumulate, uint16_t *fill,
+                         uint32_t *zbuf, nid_reffill_counts *counts) {
+  const int rows = S.rows, cols = S.cols;
+  nid_reffill_counts n = {};
+  splat_host(S, zbuf, &n.n_target_valid, &n.n_splat);
   for (int r = 0; r < rows; r++)
     for (int c = 0; c < cols; c++) {
       const size_t i = (size_t)r * (size_t)cols + (size_t)c;

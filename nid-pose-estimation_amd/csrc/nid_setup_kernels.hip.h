@@ -2,13 +2,14 @@
 // stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
 // next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth), the depth-consistency check of the
 // keyframe's points against the target's depth (k_depth_check), the reference mask (k_refmask_classify,
-// k_refmask_dilate_apply), the reference fill (k_reffill_splat, k_reffill_apply).
+// k_refmask_dilate_apply), the reference fill (k_reffill_splat, k_reffill_apply), the reference fusion (k_reffuse_apply).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
 #include "nid_depth_check.h"
 #include "nid_kernels.hip.h"
 #include "nid_reffill_rule.h"
+#include "nid_reffuse_rule.h"
 
 namespace nid {
 
@@ -435,6 +436,62 @@ __global__ void __launch_bounds__(256) k_reffill_apply(int rows, int cols, int g
     pristine[i] = f ? f : up;
   }
   counts_to_totals<2>(part, tid, totals, (int)n.n_hit, (int)n.n_holes, (int)n.n_refused, (int)n.n_new, (int)n.n_filled);
+}
+
+// The reference fusion (nid/nid_reffuse.h): k_reffill_splat as it is, then
+//
+// k_reffuse_apply: image order, no halo -- a pixel's new state hangs on its own entries alone.  A lane makes kRuPerLane
+// CONSECUTIVE pixels: the z-buffer's and the SUM plane's entries as one 16-byte access each, the u16 planes' as 8 bytes, the
+// OBS plane's as 4 (the planes come from hipMalloc and a lane's first index is a multiple of 4: aligned); a wave's accesses
+// are adjacent.  The lane whose four pixels cross the plane's end makes the ones inside it one by one.  Each pixel runs
+// rfu::fuse (nid_reffuse_rule.h: the host's text): S and k written back, the FUSED plane, the BASE plane fused-or-uploaded
+// and the new pristine depth fill-or-base for the masking chain behind this kernel.  n_hit and the rule's five counts are
+// summed like the fill's and added to words 2 .. 7 of the call's totals with ONE 64-bit INTEGER atomic each; every lane
+// reaches the shuffles.  No float is summed.
+constexpr int kRuPerLane = 4, kRuSpan = 256 * kRuPerLane;
+static_assert(sizeof(nid_reffuse_counts) == 64 && offsetof(nid_reffuse_counts, n_hit) == 16 && offsetof(nid_reffuse_counts, n_changed) == 56,
+              "nid_reffuse.h's record: the splat's two counts, then this kernel's six");
+
+__global__ void __launch_bounds__(256) k_reffuse_apply(long N, int gate_abs, int gate_rel_1024, int max_obs, const uint32_t *__restrict__ zbuf,
+                                                       const uint16_t *__restrict__ uploaded, double factor0, const uint16_t *__restrict__ fill,
+                                                       uint32_t *__restrict__ sum, uint8_t *__restrict__ obs, uint16_t *__restrict__ fused,
+                                                       uint16_t *__restrict__ base, uint16_t *__restrict__ pristine,
+                                                       unsigned long long *__restrict__ totals /*[8]: words 2 .. 7*/) {
+  __shared__ unsigned long long part[4][8];
+  const int tid = threadIdx.x;
+  const long i0 = ((long)blockIdx.x * 256 + tid) * kRuPerLane;
+  nid_reffuse_counts n = {};
+  if (i0 + kRuPerLane <= N) {
+    const uint4 z4 = *reinterpret_cast<const uint4 *>(zbuf + i0);
+    const ushort4 u4 = *reinterpret_cast<const ushort4 *>(uploaded + i0);
+    const ushort4 f4 = *reinterpret_cast<const ushort4 *>(fill + i0);
+    uint4 s4 = *reinterpret_cast<const uint4 *>(sum + i0);
+    uchar4 k4 = *reinterpret_cast<const uchar4 *>(obs + i0);
+    ushort4 e4, b4, p4;
+#define NID_RU_PIXEL(m)                                                                                                              \
+  e4.m = rfu::fuse(dc::depth_valid(u4.m, factor0), u4.m, z4.m, gate_abs, gate_rel_1024, max_obs, &s4.m, &k4.m, &b4.m, &n); \
+  p4.m = f4.m ? f4.m : b4.m;
+    NID_RU_PIXEL(x) NID_RU_PIXEL(y) NID_RU_PIXEL(z) NID_RU_PIXEL(w)
+#undef NID_RU_PIXEL
+    *reinterpret_cast<uint4 *>(sum + i0) = s4;
+    *reinterpret_cast<uchar4 *>(obs + i0) = k4;
+    *reinterpret_cast<ushort4 *>(fused + i0) = e4;
+    *reinterpret_cast<ushort4 *>(base + i0) = b4;
+    *reinterpret_cast<ushort4 *>(pristine + i0) = p4;
+  } else {
+    for (long i = i0; i < N; i++) {  // (at most kRuPerLane - 1 pixels of one lane of the grid)
+      uint32_t s = sum[i];
+      uint8_t k = obs[i];
+      uint16_t b = 0;
+      const uint16_t u = uploaded[i], f = fill[i];
+      fused[i] = rfu::fuse(dc::depth_valid(u, factor0), u, zbuf[i], gate_abs, gate_rel_1024, max_obs, &s, &k, &b, &n);
+      sum[i] = s;
+      obs[i] = k;
+      base[i] = b;
+      pristine[i] = f ? f : b;
+    }
+  }
+  counts_to_totals<2>(part, tid, totals, (int)n.n_hit, (int)n.n_valid, (int)n.n_fused, (int)n.n_gated, (int)n.n_saturated, (int)n.n_changed);
 }
 
 // depth pixels that belong to no cell (rows/cols not divisible by cell_num, Q11)
