@@ -65,9 +65,12 @@
  * nearest-pixel splat.  Where those exceed the sensor's noise a fusion makes the keyframe's depth worse, not better
  * (profiles/reffuse_cost.txt has such a sequence); the gate bounds the damage, it does not prevent it.
  *
- * Out of scope: refining fills (only sensor-valid pixels are refined), sub-pixel or bilinear splatting, confidence weights
- * beyond the observation cap, one shared splat and rebuild for a frame's fill, fusion and mask (today three chains), cell
- * shards, several devices, planes on the coarser levels.
+ * A bilinear sample of the target's depth where the keyframe pixel projects, in the place of the nearest-pixel splat, is
+ * nid_refgather.h's: the same state, gate and cap, another source of the observation.
+ *
+ * Out of scope: refining fills (only sensor-valid pixels are refined), confidence weights beyond the observation cap, one
+ * shared splat and rebuild for a frame's fill, fusion and mask (today three chains), cell shards, several devices, planes on
+ * the coarser levels.
  */
 #ifndef NID_REFFUSE_H
 #define NID_REFFUSE_H

@@ -139,6 +139,13 @@ REFFUSE_COUNTS_DTYPE = np.dtype([("n_target_valid", "i8"), ("n_splat", "i8"), ("
                                  ("n_gated", "i8"), ("n_saturated", "i8"), ("n_changed", "i8")])
 assert REFFUSE_COUNTS_DTYPE.itemsize == 64
 
+# include/nid/nid_refgather.h (likewise: bilinear depth samples fused into the reference, the tracker's use of them)
+REFGATHER_SYMBOLS = ["nid_pyr_fuse_reference_depth_bilinear", "nid_refgather_host", "nid_track_set_fusion_sampling", "nid_track_last_gather"]
+REFFUSE_NEAREST, REFFUSE_BILINEAR = 0, 1
+REFGATHER_COUNTS_DTYPE = np.dtype([("n_valid", "i8"), ("n_sampled", "i8"), ("n_outside", "i8"), ("n_tap_refused", "i8"), ("n_fused", "i8"),
+                                   ("n_gated", "i8"), ("n_saturated", "i8"), ("n_changed", "i8")])
+assert REFGATHER_COUNTS_DTYPE.itemsize == 64
+
 _lib = None
 
 
@@ -293,6 +300,13 @@ def load():
                                          C.POINTER(C.c_uint32), c_u8p, u16p, vp]
         lib.nid_track_set_fusing.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int]
         lib.nid_track_last_fusion.argtypes = [vp, vp]
+    if hasattr(lib, "nid_pyr_fuse_reference_depth_bilinear"):   # (likewise)
+        u16p = C.POINTER(C.c_uint16)
+        lib.nid_pyr_fuse_reference_depth_bilinear.argtypes = [vp, c_dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+        lib.nid_refgather_host.argtypes = [C.POINTER(NidConfig), u16p, C.c_double, c_dp, u16p, C.c_double, c_dp, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.POINTER(C.c_uint32), c_u8p, u16p, vp]
+        lib.nid_track_set_fusion_sampling.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        lib.nid_track_last_gather.argtypes = [vp, vp]
     _lib = lib
     return lib
 
@@ -876,6 +890,16 @@ class Pyramid:
                                                           n.ctypes.data_as(C.c_void_p)), "nid_pyr_fuse_reference_depth")
         return n[0]
 
+    def fuse_reference_depth_bilinear(self, pose7, gate_abs=50, gate_rel_1024=20, max_obs=255, tap_abs=50, tap_rel_1024=20):
+        """nid_pyr_fuse_reference_depth_bilinear (nid_refgather.h): the counts as a REFGATHER_COUNTS_DTYPE record."""
+        q = _d(pose7)
+        assert q.size == 7
+        n = np.zeros(1, dtype=REFGATHER_COUNTS_DTYPE)
+        self._check(self.lib.nid_pyr_fuse_reference_depth_bilinear(self.h, _dp(q), int(gate_abs), int(gate_rel_1024), int(max_obs), int(tap_abs),
+                                                                   int(tap_rel_1024), n.ctypes.data_as(C.c_void_p)),
+                    "nid_pyr_fuse_reference_depth_bilinear")
+        return n[0]
+
     def clear_reference_fusion(self):
         self._check(self.lib.nid_pyr_clear_reference_fusion(self.h), "nid_pyr_clear_reference_fusion")
 
@@ -1067,6 +1091,16 @@ class Tracker:
         self._check(self.lib.nid_track_last_fusion(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_fusion")
         return n[0]
 
+    def set_fusion_sampling(self, mode, tap_abs=50, tap_rel_1024=20):
+        """nid_track_set_fusion_sampling (nid_refgather.h): REFFUSE_NEAREST by default"""
+        self._check(self.lib.nid_track_set_fusion_sampling(self.h, int(mode), int(tap_abs), int(tap_rel_1024)), "nid_track_set_fusion_sampling")
+
+    def last_gather(self):
+        """nid_track_last_gather: the counts of the last push's gather as a REFGATHER_COUNTS_DTYPE record (zeros: it ran none)"""
+        n = np.zeros(1, dtype=REFGATHER_COUNTS_DTYPE)
+        self._check(self.lib.nid_track_last_gather(self.h, n.ctypes.data_as(C.c_void_p)), "nid_track_last_gather")
+        return n[0]
+
     def push(self, im, depth_u16=None, depth_factor=1.0 / 5000, T_wc_first=None):
         """nid_track_push_u16: one frame.  Returns a dict of nid_track_result's members (pose7 and rounds as arrays)."""
         N = self.cfg0.rows * self.cfg0.cols
@@ -1174,6 +1208,31 @@ def reffuse_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1,
                               f.ctypes.data_as(u16p), n.ctypes.data_as(C.c_void_p))
     if rc != NID_OK:
         raise NidError(f"nid_reffuse_host: {lib.nid_status_string(rc).decode()} ({rc})")
+    shape = (cfg.rows, cfg.cols)
+    return s.reshape(shape), k.reshape(shape), f.reshape(shape), n[0]
+
+
+def refgather_host(cfg, depth0_u16, factor0, T_wc_colmajor16, depth1_u16, factor1, pose7, gate_abs=50, gate_rel_1024=20, max_obs=255,
+                   tap_abs=50, tap_rel_1024=20, sums=None, obs=None):
+    """nid_refgather_host (nid_refgather.h): one call of the rule on copies of `sums` and `obs` (None: zeros): (SUM plane
+    [rows, cols] u32, OBS plane u8, FUSED plane u16, counts as a REFGATHER_COUNTS_DTYPE record) -- what
+    nid_pyr_fuse_reference_depth_bilinear computes, from the same text compiled for the host."""
+    lib = load()
+    N = cfg.rows * cfg.cols
+    u16p = C.POINTER(C.c_uint16)
+    d0 = np.ascontiguousarray(depth0_u16, dtype=np.uint16).reshape(-1)
+    d1 = np.ascontiguousarray(depth1_u16, dtype=np.uint16).reshape(-1)
+    T, q = _d(T_wc_colmajor16), _d(pose7)
+    s = np.zeros(N, dtype=np.uint32) if sums is None else np.array(sums, dtype=np.uint32).reshape(-1)
+    k = np.zeros(N, dtype=np.uint8) if obs is None else np.array(obs, dtype=np.uint8).reshape(-1)
+    f = np.zeros(N, dtype=np.uint16)
+    assert d0.size == N and d1.size == N and s.size == N and k.size == N and T.size == 16 and q.size == 7
+    n = np.zeros(1, dtype=REFGATHER_COUNTS_DTYPE)
+    rc = lib.nid_refgather_host(C.byref(cfg), d0.ctypes.data_as(u16p), float(factor0), _dp(T), d1.ctypes.data_as(u16p), float(factor1), _dp(q),
+                                int(gate_abs), int(gate_rel_1024), int(max_obs), int(tap_abs), int(tap_rel_1024),
+                                s.ctypes.data_as(C.POINTER(C.c_uint32)), k.ctypes.data_as(c_u8p), f.ctypes.data_as(u16p), n.ctypes.data_as(C.c_void_p))
+    if rc != NID_OK:
+        raise NidError(f"nid_refgather_host: {lib.nid_status_string(rc).decode()} ({rc})")
     shape = (cfg.rows, cfg.cols)
     return s.reshape(shape), k.reshape(shape), f.reshape(shape), n[0]
 

@@ -2164,3 +2164,6 @@ int64_t nid_contract_bytes(const nid_ctx *ctx) {
 
 // ---- the reference's valid depth refined from tracked frames and the tracker's use of it (include/nid/nid_reffuse.h) ---
 #include "nid_reffuse.inc"
+
+// ---- bilinear depth samples fused into the reference and the tracker's use of them (include/nid/nid_refgather.h) --------
+#include "nid_refgather.inc"

@@ -63,7 +63,12 @@ int track_finish_with_policy(nid_track *t, int n, nid_track_result *R, nid_depth
     // (nid_reffill.h): the keyframe stays, with this frame's depth where it has none; the first fill of a pixel stays
     if (t->fill_on && (rc = nid_pyr_fill_reference_depth(p, best.pose7, t->fill_guard, t->fill_guard_abs, t->fill_guard_rel_1024, 1, &t->push_fill))) return rc;
     // (nid_reffuse.h): ... and this frame's depth averaged into the samples it has, where it passes their gate
-    if (t->fuse_on && (rc = nid_pyr_fuse_reference_depth(p, best.pose7, t->fuse_gate_abs, t->fuse_gate_rel_1024, t->fuse_max_obs, &t->push_fusion))) return rc;
+    // (nid_refgather.h): ... from bilinear samples of it where the caller asked for them
+    if (t->fuse_on && t->fuse_sampling == NID_REFFUSE_BILINEAR) {
+      if ((rc = nid_pyr_fuse_reference_depth_bilinear(p, best.pose7, t->fuse_gate_abs, t->fuse_gate_rel_1024, t->fuse_max_obs, t->fuse_tap_abs,
+                                                      t->fuse_tap_rel_1024, &t->push_gather)))
+        return rc;
+    } else if (t->fuse_on && (rc = nid_pyr_fuse_reference_depth(p, best.pose7, t->fuse_gate_abs, t->fuse_gate_rel_1024, t->fuse_max_obs, &t->push_fusion))) return rc;
     // 5e. (nid_refmask.h): ... without what this frame no longer sees of it
     if (t->mask_classes && (rc = nid_pyr_mask_occluded(p, best.pose7, P.tol_abs, P.tol_rel, t->mask_classes, t->mask_dilate, 0, &t->push_mask))) return rc;
   }

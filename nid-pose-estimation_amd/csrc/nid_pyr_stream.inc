@@ -38,6 +38,10 @@ struct nid_track {
   bool fuse_on = false;
   int32_t fuse_gate_abs = 0, fuse_gate_rel_1024 = 0, fuse_max_obs = 1;
   nid_reffuse_counts last_fusion = {}, push_fusion = {};  // (push_fusion: as push_mask)
+  // nid_refgather.h (nid_refgather.inc): where such a fusion takes its observations from, the tap gate of a bilinear one, and
+  // the counts of the last push's gather
+  int32_t fuse_sampling = NID_REFFUSE_NEAREST, fuse_tap_abs = 0, fuse_tap_rel_1024 = 0;
+  nid_refgather_counts last_gather = {}, push_gather = {};  // (push_gather: as push_mask)
 };
 
 namespace {
@@ -196,6 +200,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   t->push_mask = nid_refmask_counts();  // (nid_refmask.h: step 5e's counts, if this push runs it)
   t->push_fill = nid_reffill_counts();  // (nid_reffill.h: the fill's counts, likewise)
   t->push_fusion = nid_reffuse_counts();  // (nid_reffuse.h: the fusion's)
+  t->push_gather = nid_refgather_counts();  // (nid_refgather.h: the gather's)
   int rc = nid_pyr_set_target_u8(p, im);
   if (rc) return rc;
   if (first) {
@@ -261,6 +266,7 @@ int nid_track_push_u16(nid_track *t, const uint16_t *depth_u16, double depth_fac
   t->last_mask = t->push_mask;
   t->last_fill = t->push_fill;
   t->last_fusion = t->push_fusion;
+  t->last_gather = t->push_gather;
   t->frame++;
   *out = R;
   return NID_OK;

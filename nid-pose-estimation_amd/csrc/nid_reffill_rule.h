@@ -54,6 +54,17 @@ inline void target_to_keyframe(const double *Twc16, const double *pose7, double 
   lm::pose_record(rel, 0, q7, M, &mode);
 }
 
+// K: the composition the other way round, x_t = T_cw(target) T_wc(keyframe) x_k (nid_refgather_rule.h projects the
+// keyframe's pixels with it).  Host only, once per call, on the same terms.
+inline void keyframe_to_target(const double *Twc16, const double *pose7, double *K) {
+  double kf[7], inv[7], rel[7], q7[7];
+  int32_t mode;
+  track::pose_from_Twc16(Twc16, kf);
+  track::pose_inverse(kf, inv);
+  track::pose_compose(pose7, inv, rel);
+  lm::pose_record(rel, 0, q7, K, &mode);
+}
+
 // Part A for target pixel (r1, c1).  0: its depth is not valid; 1: valid, and it ends before the z-buffer; 2: a splat of
 // count *q onto keyframe pixel *idx (row-major, inside the image).
 NID_DC_HD int splat(const Splat &S, int r1, int c1, size_t *idx, uint32_t *q) {

@@ -2,7 +2,8 @@
 // stage at the initial pose (k_href), the plain-histogram program (k_plain_nid), untiling of the per-pixel outputs, the
 // next pyramid level (k_pyr_down; one plane of it: k_pyr_down_u8, k_pyr_down_depth), the depth-consistency check of the
 // keyframe's points against the target's depth (k_depth_check), the reference mask (k_refmask_classify,
-// k_refmask_dilate_apply), the reference fill (k_reffill_splat, k_reffill_apply), the reference fusion (k_reffuse_apply).
+// k_refmask_dilate_apply), the reference fill (k_reffill_splat, k_reffill_apply), the reference fusion (k_reffuse_apply), the
+// bilinear gather of the same fusion (k_refgather_apply).
 // Streaming kernels, not on the iteration path.  Included by ONE translation unit (nid_capi.hip), which launches them.
 #pragma once
 
@@ -10,6 +11,7 @@
 #include "nid_kernels.hip.h"
 #include "nid_reffill_rule.h"
 #include "nid_reffuse_rule.h"
+#include "nid_refgather_rule.h"
 
 namespace nid {
 
@@ -492,6 +494,72 @@ __global__ void __launch_bounds__(256) k_reffuse_apply(long N, int gate_abs, int
     }
   }
   counts_to_totals<2>(part, tid, totals, (int)n.n_hit, (int)n.n_valid, (int)n.n_fused, (int)n.n_gated, (int)n.n_saturated, (int)n.n_changed);
+}
+
+// The bilinear gather (nid/nid_refgather.h): ONE kernel in the place of k_reffill_splat, the z-buffer's fill and
+// k_reffuse_apply.
+//
+// k_refgather_apply: image order, k_reffuse_apply's shape -- a lane makes kRuPerLane CONSECUTIVE pixels, the SUM plane's
+// entries as one 16-byte access, the u16 planes' as 8 bytes, the OBS plane's as 4; the lane whose four pixels cross the
+// plane's end makes the ones inside it one by one.  Each pixel runs rg::gather (nid_refgather_rule.h: the host's text):
+// the f64 chain G.1 - G.6 -- seven divisions, none of them in a loop -- and four 2-byte reads of the target's depth where
+// the pixel projects.  Neighbouring keyframe pixels project onto neighbouring target pixels, so a wave's taps fall into a
+// few rows' worth of lines and the plane (tens of kilobytes) stays in L2; the kernel's time is the f64 VALU chain's, not
+// the reads'.  The eight counts are summed like the fusion's and added to the call's eight totals with ONE 64-bit INTEGER
+// atomic each; every lane reaches the shuffles.  No float is summed, no atomic touches a plane.
+struct RefGatherArgs {
+  double K[12];        // rows of [R|t], keyframe camera -> target camera (rf::keyframe_to_target)
+  double M[12];        // rows of [R|t], target camera -> keyframe camera (rf::target_to_keyframe)
+  const uint16_t *d1;  // the target's depth, rows x cols
+  double factor1, factor0;
+  int tap_abs, tap_rel_1024;
+};
+static_assert(sizeof(nid_refgather_counts) == 64 && offsetof(nid_refgather_counts, n_changed) == 56, "nid_refgather.h's record: this kernel's eight counts");
+
+__global__ void __launch_bounds__(256) k_refgather_apply(Geometry g, RefGatherArgs A, long N, int gate_abs, int gate_rel_1024, int max_obs,
+                                                         const uint16_t *__restrict__ uploaded, const uint16_t *__restrict__ fill,
+                                                         uint32_t *__restrict__ sum, uint8_t *__restrict__ obs, uint16_t *__restrict__ fused,
+                                                         uint16_t *__restrict__ base, uint16_t *__restrict__ pristine,
+                                                         unsigned long long *__restrict__ totals /*[8], zero before the launch*/) {
+  __shared__ unsigned long long part[4][8];
+  const int tid = threadIdx.x;
+  const long i0 = ((long)blockIdx.x * 256 + tid) * kRuPerLane;
+  nid_refgather_counts n = {};
+  const rg::Gather G = rg::make_gather(g, A.K, A.M, A.d1, A.factor1, A.factor0, A.tap_abs, A.tap_rel_1024);
+  int r = (int)(i0 / g.cols), c = (int)(i0 % g.cols);  // (the lane's first pixel; the next ones step along the row)
+  if (i0 + kRuPerLane <= N) {
+    const ushort4 u4 = *reinterpret_cast<const ushort4 *>(uploaded + i0);
+    const ushort4 f4 = *reinterpret_cast<const ushort4 *>(fill + i0);
+    uint4 s4 = *reinterpret_cast<const uint4 *>(sum + i0);
+    uchar4 k4 = *reinterpret_cast<const uchar4 *>(obs + i0);
+    ushort4 e4, b4, p4;
+#define NID_RG_PIXEL(m)                                                                                 \
+  e4.m = rg::gather(G, r, c, u4.m, gate_abs, gate_rel_1024, max_obs, &s4.m, &k4.m, &b4.m, &n); \
+  p4.m = f4.m ? f4.m : b4.m;                                                                            \
+  if (++c == g.cols) { c = 0; r++; }
+    NID_RG_PIXEL(x) NID_RG_PIXEL(y) NID_RG_PIXEL(z) NID_RG_PIXEL(w)
+#undef NID_RG_PIXEL
+    *reinterpret_cast<uint4 *>(sum + i0) = s4;
+    *reinterpret_cast<uchar4 *>(obs + i0) = k4;
+    *reinterpret_cast<ushort4 *>(fused + i0) = e4;
+    *reinterpret_cast<ushort4 *>(base + i0) = b4;
+    *reinterpret_cast<ushort4 *>(pristine + i0) = p4;
+  } else {
+    for (long i = i0; i < N; i++) {  // (at most kRuPerLane - 1 pixels of one lane of the grid)
+      uint32_t s = sum[i];
+      uint8_t k = obs[i];
+      uint16_t b = 0;
+      const uint16_t f = fill[i];
+      fused[i] = rg::gather(G, r, c, uploaded[i], gate_abs, gate_rel_1024, max_obs, &s, &k, &b, &n);
+      sum[i] = s;
+      obs[i] = k;
+      base[i] = b;
+      pristine[i] = f ? f : b;
+      if (++c == g.cols) { c = 0; r++; }
+    }
+  }
+  counts_to_totals<0>(part, tid, totals, (int)n.n_valid, (int)n.n_sampled, (int)n.n_outside, (int)n.n_tap_refused, (int)n.n_fused, (int)n.n_gated,
+                      (int)n.n_saturated, (int)n.n_changed);
 }
 
 // depth pixels that belong to no cell (rows/cols not divisible by cell_num, Q11)
